@@ -15,14 +15,18 @@ torch.distributed.run the ranks come from the environment; `--gpus N` without it
 rank processes itself (before anything touches a GPU).  The barrier and the max-over-ranks
 time go through gloo on the host: no RCCL on this path.
 
-Outside the timed region: per-launch HIP-event times (the dominant kernel's roofline), a
-parity check of sampled frames against the float64 oracle (checker only), and the
-end-to-end host path (single-frame latency; streaming from pinned host memory with the H2D
-copy of batch k+1 overlapping the compute of batch k).
+A plain run sets up, warms up, times exactly --steps steps, writes the last step's outputs
+when --dump-outputs DIR is given (DIR/rows.npy, DIR/waterfall.npy, float32; the inputs are
+seeded, so two builds can be compared array for array) and prints the result line.
 
-CPU baseline: the reference's numpy/scipy library path (oracle/scipy_path.py, the same
-decimate/welch calls) on a bounded sample of frames, rank 0 at N=1 only, in a spawn-context
-process pool of the job's CPU share, run BEFORE the GPU is touched.
+Only with --full, outside the timed region: per-launch HIP-event times (the dominant
+kernel's roofline), a parity check of sampled frames against the float64 oracle (checker
+only), and the end-to-end host path (single-frame latency; streaming from pinned host
+memory with the H2D copy of batch k+1 overlapping the compute of batch k).
+
+CPU baseline (--full only): the reference's numpy/scipy library path (oracle/scipy_path.py,
+the same decimate/welch calls) on a bounded sample of frames, rank 0 at N=1 only, in a
+spawn-context process pool of the job's CPU share, run BEFORE the GPU is touched.
 """
 from __future__ import annotations
 
@@ -272,6 +276,29 @@ def decoded_host(torch, xe, f, in_dtype):
     return a[:, 0] + 1j * a[:, 1]
 
 
+DUMP_MAX_BYTES = 30_000_000  # per array; two arrays stay under 64 MB together
+
+
+def bounded_sample(a, seed):
+    """`a` itself, or a fixed seeded sample of its rows (in order) within DUMP_MAX_BYTES."""
+    import numpy as np
+    n = DUMP_MAX_BYTES // max(1, a[0].nbytes)
+    if a.shape[0] <= n:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=n, replace=False))
+    return np.ascontiguousarray(a[idx])
+
+
+def dump_outputs(path, plan, rows, rank, world):
+    """What the last timed step handed its caller: the F dB rows and the waterfall image
+    after the push of those rows, float32, as <name>.npy (<name>_rank<r>.npy on N > 1)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"rows{sfx}.npy"), bounded_sample(rows.cpu().numpy(), 1))
+    np.save(os.path.join(path, f"waterfall{sfx}.npy"), bounded_sample(plan.waterfall_image(), 2))
+
+
 def stamped_profile(path, F, in_dtype):
     """A committed profile summary, if it was measured on these kernel sources."""
     from pypanadapter_amd import build
@@ -394,10 +421,10 @@ def display_timing(dev, widths=(512, 8192), lines=12) -> dict:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200,
-                    help="timed steps; raised so that the timed region lasts >= --min-seconds")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="lower bound on the timed region (0: exactly --steps)")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="when > 0, raise the step count so that the timed region lasts this "
+                         "long (0: exactly --steps)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--frames", type=int, default=0, help="frames per rank (default: config)")
@@ -408,6 +435,13 @@ def main():
                     help="0 auto, 1 exact order, 2 fused interior, 3 XA tiles, 4 PC cascade")
     ap.add_argument("--welch", type=int, default=0,
                     help="Welch kernel: 0 auto, 1 one workgroup per frame, 2 four-step (A/B runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, "
+                         "per-launch times and rooflines, the oracle parity check and the "
+                         "end-to-end host path (each can be left out with --no-cpu / "
+                         "--no-check / --no-e2e)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's rows and waterfall image to DIR/*.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-workers", type=int, default=0, help="0: the job's CPU share")
     ap.add_argument("--no-cpu", action="store_true")
@@ -436,7 +470,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         share, how = cpu_share()
         workers = args.cpu_workers or share
         cpu = cpu_baseline(cfg, args.cpu_seconds, workers, how if not args.cpu_workers else "--cpu-workers")
@@ -492,7 +526,7 @@ def main():
     sp = stream.cuda_stream
     x = make_frames(torch, F, L, cfg, dev, 1234 + rank)
     xe = encode(torch, x, args.in_dtype)
-    if xe is not x and (args.no_e2e or rank != 0):
+    if xe is not x and (not args.full or args.no_e2e or rank != 0):
         x = None  # only the e2e leg re-encodes from the float frames
     rows = torch.empty((F, W), dtype=torch.float32, device=dev)
     torch.cuda.synchronize(dev)
@@ -504,14 +538,16 @@ def main():
     for _ in range(max(1, args.warmup)):
         step()
     torch.cuda.synchronize(dev)
-    t_w = time.perf_counter()  # a warm probe for the step time (the first warmup step also
-    for _ in range(3):         # allocates the plan's workspaces)
-        step()
-    torch.cuda.synchronize(dev)
-    est = (time.perf_counter() - t_w) / 3
-    # >= min_seconds of timed work whatever --steps says (a 20-step region at ~6 ms/step is
-    # 0.13 s, inside the box-to-box noise); every rank runs the same count (max over ranks)
-    steps = max(args.steps, math.ceil(1.05 * args.min_seconds / max(est, 1e-6)))
+    steps = max(1, args.steps)
+    if args.min_seconds > 0:
+        t_w = time.perf_counter()  # a warm probe for the step time (the first warmup step
+        for _ in range(3):         # also allocates the plan's workspaces)
+            step()
+        torch.cuda.synchronize(dev)
+        est = (time.perf_counter() - t_w) / 3
+        # >= min_seconds of timed work (a 20-step region at ~6 ms/step is 0.13 s, inside the
+        # box-to-box noise); every rank runs the same count (max over ranks)
+        steps = max(steps, math.ceil(1.05 * args.min_seconds / max(est, 1e-6)))
     if dist:
         ts = torch.tensor([steps], dtype=torch.int64)
         dist.all_reduce(ts, op=dist.ReduceOp.MAX)
@@ -534,17 +570,21 @@ def main():
     if dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max, ev_max = float(t[0]), float(t[1])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan, rows, rank, world)
 
-    # per-launch HIP-event times (events on the launch stream) over a few instrumented steps
-    plan.set_timing(True)
-    acc, n_inst = {}, max(1, min(steps, 10))
-    for _ in range(n_inst):
-        plan.process_device(xe.data_ptr(), L, F, rows.data_ptr(), sp)
-        for i, (nm, ms) in enumerate(zip(plan.launch_names(), plan.timings())):
-            acc[f"{i}:{nm}"] = acc.get(f"{i}:{nm}", 0.0) + ms
-    plan.set_timing(False)
-    torch.cuda.synchronize(dev)
-    kernels = {k: round(v / n_inst, 4) for k, v in acc.items()}
+    kernels = {}
+    if args.full:
+        # per-launch HIP-event times (events on the launch stream) over a few instrumented steps
+        plan.set_timing(True)
+        acc, n_inst = {}, max(1, min(steps, 10))
+        for _ in range(n_inst):
+            plan.process_device(xe.data_ptr(), L, F, rows.data_ptr(), sp)
+            for i, (nm, ms) in enumerate(zip(plan.launch_names(), plan.timings())):
+                acc[f"{i}:{nm}"] = acc.get(f"{i}:{nm}", 0.0) + ms
+        plan.set_timing(False)
+        torch.cuda.synchronize(dev)
+        kernels = {k: round(v / n_inst, 4) for k, v in acc.items()}
     finite = bool(torch.isfinite(rows).all().item())
 
     if rank != 0:
@@ -552,13 +592,13 @@ def main():
             dist.destroy_process_group()
         return
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         pick = sorted({0, F // 2, F - 1} | ({per * i + per - 1 for i in range(len(f_los))} if len(f_los) > 1 else set()))
         host_rows = rows.cpu().numpy()
         frames = {f: decoded_host(torch, xe, f, args.in_dtype) for f in pick}
         check = parity_check(frames, {f: host_rows[f] for f in pick}, cfg, f_lo_of)
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         plan.close()
         del rows
         e2e = end_to_end(torch, args, cfg, x if x is not None else xe, dev)
@@ -608,6 +648,7 @@ def main():
         "n_gpus": world,
         "steps": steps,
         "steps_requested": args.steps,
+        "full": args.full,
         "warmup": args.warmup,
         "timed_seconds": round(wall_max, 4),
         "ms_per_step": round(ms_per_step, 4),

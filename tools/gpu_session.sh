@@ -44,13 +44,13 @@ for s in $STEPS; do
     smoke)
       run smoke 400 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
     bench)
-      run bench 900 python bench.py || exit $? ;;
+      run bench 900 python bench.py --full --min-seconds 1 || exit $? ;;
     driver)  # the driver's own bench command line
       run bench_driver 900 python bench.py --gpus 1 --steps 20 --warmup 5 || exit $? ;;
     quick)
       run quick 300 python bench.py --steps 100 --warmup 3 $FAST || exit $? ;;
     cfgs)
-      CHK="--no-cpu --no-e2e"
+      CHK="--full --no-cpu --no-e2e"
       run bench_cfg3 300 python bench.py --config cfg3 --steps 50 --warmup 2 $CHK || exit $?
       run bench_cfg5 300 python bench.py --config cfg5 --steps 20 --warmup 2 $CHK || exit $?
       run bench_cfg5_f16 300 python bench.py --config cfg5 --in-dtype complex32 --steps 20 --warmup 2 $CHK || exit $?
