@@ -20,7 +20,8 @@
 // the join: exact minus the zero-extended model), which g's truncation changes by < 2e-8.
 //
 // Work per input sample: ~30 VALU lane-instructions (the walk: 74); LDS: two
-// exchanges of the 8192-point window plus five small ones of the 1024-point inverse per block.
+// exchanges of the 8192-point window plus three small ones of the 1024-point inverse per block
+// (inverse stages 2..4 exchange between a wave's lanes in registers).
 #include <algorithm>
 
 #include "zfft_device.h"
@@ -31,7 +32,9 @@
 // results by design: FC_KO 1 the input loads (window values from registers), 2 the filter-table
 // loads, 4 the output stores (profiles/r06fc/r06fc4: 2.84 ms -> 1.85 / 2.61 / 2.54, all three
 // 1.56 at K = 1024).  Measured and removed: the filter table requested before the prefetch
-// (2.98 ms, spills) and the prefetch requested after the table (2.80, r06fc5).
+// (2.98 ms, spills) and the prefetch requested after the table (2.80, r06fc5; again with the
+// block head's drain gone: 3.17 against 3.00 ms per step, r07fc) and the table requested before
+// the barrier that ends pass B (2.90 against 2.88, r07fc).
 #ifndef ZFFT_DIAG
 #define ZFFT_DIAG 0
 #endif
@@ -41,8 +44,20 @@
 #ifndef FC_KO
 #define FC_KO 0
 #endif
-#ifndef FC_WSYNC
-#define FC_WSYNC 1  // A/B knob: 0 = a workgroup barrier between the wave-local inverse stages
+// A/B knobs (build(defines=...)), the defaults are what ships:
+#ifndef FC_INV_LDS
+#define FC_INV_LDS 0  // 1 = inverse stages 2..4 exchange through LDS instead of between lanes
+#endif
+#ifndef FC_HEAD_DRAIN
+#define FC_HEAD_DRAIN 0  // 1 = the block head as before: no wait closing the edge path, plain pointers
+#endif
+#ifndef FC_CTAB_ORDER
+#define FC_CTAB_ORDER 1  // 0 = pass C's table pairs held and requested in storage order
+#endif
+#if FC_HEAD_DRAIN
+#define FC_RESTRICT
+#else
+#define FC_RESTRICT __restrict__
 #endif
 #ifndef FC_HOLD
 #define FC_HOLD (-1)  // diagnostic override of fc_hold for every non-cu8 instantiation
@@ -161,18 +176,62 @@ __device__ __forceinline__ typename RawP<DT>::T load_pair_b(__amdgpu_buffer_rsrc
   else if constexpr (DT == kInCU8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, so, aux));
   else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, aux));
 }
-// Between two inverse stages whose LDS slots stay inside one wave: a wave's LDS operations
-// complete in issue order, so ordering the compiler's view (wavefront-scope fences around a
-// wave barrier) is all it takes -- no s_barrier
-__device__ __forceinline__ void stage_sync() {
-  if (FC_WSYNC) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  } else {
-    __syncthreads();
-  }
+// Between two inverse stages whose elements stay inside one wave, the exchange is a 4 x 4
+// transpose of a lane's register index a against two bits of its lane number, one bit at a time
+// and one dword at a time (tests/test_fc_lane_exchange.py models exactly this sequence).
+// Bits 5:4 (stage 2 -> 3): v_permlane32_swap exchanges the upper 32 lanes of its first operand
+// with the lower 32 of its second, v_permlane16_swap the odd 16-lane rows of the first with the
+// even rows of the second.  (fbits takes the float by value: __builtin_bit_cast applied to a
+// vector element through a reference read element 0 for .y as well.)
+__device__ __forceinline__ unsigned fbits(float f) { return __builtin_bit_cast(unsigned, f); }
+__device__ __forceinline__ float bitsf(unsigned u) { return __builtin_bit_cast(float, u); }
+__device__ __forceinline__ void swap32(v2f &a, v2f &b) {
+  const auto x = __builtin_amdgcn_permlane32_swap(fbits(a.x), fbits(b.x), false, false);
+  const auto y = __builtin_amdgcn_permlane32_swap(fbits(a.y), fbits(b.y), false, false);
+  a = v2f{bitsf(x[0]), bitsf(y[0])};
+  b = v2f{bitsf(x[1]), bitsf(y[1])};
 }
+__device__ __forceinline__ void swap16(v2f &a, v2f &b) {
+  const auto x = __builtin_amdgcn_permlane16_swap(fbits(a.x), fbits(b.x), false, false);
+  const auto y = __builtin_amdgcn_permlane16_swap(fbits(a.y), fbits(b.y), false, false);
+  a = v2f{bitsf(x[0]), bitsf(y[0])};
+  b = v2f{bitsf(x[1]), bitsf(y[1])};
+}
+// Bits 3:2 (stage 3 -> 4), inside a 16-lane row: the lanes with lane bit SH set take b from SH
+// lanes below into a (DPP row_shr, bank mask = those lanes' banks of 4), the others a from SH
+// lanes above into b (row_shl); a masked-off lane keeps what it had.
+template <int SH>
+__device__ __forceinline__ void swap_row(v2f &a, v2f &b) {
+  constexpr int hi = SH == 8 ? 0xc : 0xa, lo = 0xf ^ hi;
+  const unsigned ax = fbits(a.x), ay = fbits(a.y), bx = fbits(b.x), by = fbits(b.y);
+  a = v2f{bitsf(__builtin_amdgcn_update_dpp(ax, bx, 0x110 + SH, 0xf, hi, false)),
+          bitsf(__builtin_amdgcn_update_dpp(ay, by, 0x110 + SH, 0xf, hi, false))};
+  b = v2f{bitsf(__builtin_amdgcn_update_dpp(bx, ax, 0x100 + SH, 0xf, lo, false)),
+          bitsf(__builtin_amdgcn_update_dpp(by, ay, 0x100 + SH, 0xf, lo, false))};
+}
+// lane l, register a: element l + 64 a -> (l & 15) + 16 a + 64 (l >> 4)
+__device__ __forceinline__ void xchg_54(v2f *v) {
+  swap32(v[0], v[2]);
+  swap32(v[1], v[3]);
+  swap16(v[0], v[1]);
+  swap16(v[2], v[3]);
+}
+// -> (l & 3) + 4 a + 16 ((l >> 2) & 3) + 64 (l >> 4)
+__device__ __forceinline__ void xchg_32(v2f *v) {
+  swap_row<8>(v[0], v[2]);
+  swap_row<8>(v[1], v[3]);
+  swap_row<4>(v[0], v[1]);
+  swap_row<4>(v[2], v[3]);
+}
+#if FC_INV_LDS
+// the LDS form of the same exchanges: a wave's LDS operations complete in issue order, so
+// ordering the compiler's view (wavefront-scope fences around a wave barrier) is all it takes
+__device__ __forceinline__ void stage_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+#endif
 
 // How many of a thread's 16 C pairs stay in registers for the whole kernel instead of being
 // re-read from L2 every block: as many as each instantiation holds without spilling at 2 WG/CU
@@ -186,9 +245,9 @@ constexpr int fc_hold(int Z, int DT) {
 // then per LO row (row_stride apart) C as v4f pairs [(Z / 2) k3 + r / 2][t] (r, r + 1) for thread t
 // of pass C.  Needs frames of >= kFcN samples and < 2^31 bytes (launch_fc_decim).
 template <int Z, int DT, int FLIP>
-__global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *lo, const v2f *tab,
-                                                         int64_t row_stride, v2f *out, int64_t nd,
-                                                         int bpc) {
+__global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *FC_RESTRICT lo,
+                                                         const v2f *FC_RESTRICT tab, int64_t row_stride,
+                                                         v2f *FC_RESTRICT out, int64_t nd, int bpc) {
   constexpr int M = kN / Z;             // per-residue transform: 1024 (zoom 8), 2048 (zoom 4)
   constexpr int R1 = M / 256;           // radix of the last forward / first inverse stage
   constexpr int S = Geo<Z>::S, K = Geo<Z>::K, P = Geo<Z>::P;
@@ -224,12 +283,16 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   }
   // pass C: k1 = t >> 4, k2 = t & 15 -> kp = k1 + 16 k2
   const int kp = (t >> 4) + 16 * (t & 15);
-  // the first HOLD of its 16 C pairs held for the whole kernel (the rest read per block)
+  // HOLD of its 16 C pairs held for the whole kernel, the rest read per block.  Pass C takes
+  // pair (Z / 2) k + rp in its round rp: cix(j) is the j-th pair in that order, and the pairs are
+  // held and requested in it, so the first rounds need no load and every later wait leaves
+  // the requests of the rounds after it in flight.
   constexpr int HOLD = FC_HOLD >= 0 ? (DT == kInCU8 ? 0 : FC_HOLD) : fc_hold(Z, DT);
+  auto cix = [](int j) { return FC_CTAB_ORDER ? (Z / 2) * (j % R1) + j / R1 : j; };
   v4f ch[HOLD > 0 ? HOLD : 1];
 #pragma unroll
-  for (int i = 0; i < HOLD; ++i)
-    ch[i] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(crs, (uint32_t)(16 * t), 4096 * i, 0));
+  for (int j = 0; j < HOLD; ++j)
+    ch[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(crs, (uint32_t)(16 * t), 4096 * cix(j), 0));
   // inverse twiddle bases, conjugated: stage 1 W_M^kp, 2 W_256^(t & 63), 3 W_64^(t & 15),
   // 4 W_16^(t & 3) (the digits below each stage's)
   const v2f ib0 = conj(tw[kp]), ib1 = conj(tw[(M / 256) * (t & 63)]), ib2 = conj(tw[(M / 64) * (t & 15)]),
@@ -252,7 +315,9 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   const int a1 = ps(kp);                               // ps(kp + 256 q) = a1 + 272 q
   // stages 2..4 (butterfly t + 256 h at +1088 h), stage 5
   const int a2 = ps((t & 63) + 256 * (t >> 6));                                      // + 68 a
+#if FC_INV_LDS
   const int a3 = ps((t & 15) + 64 * ((t >> 4) & 3) + 256 * (t >> 6));               // + 17 a
+#endif
   const int a4 = ps((t & 3) + 16 * ((t >> 2) & 3) + 64 * ((t >> 4) & 3) + 256 * (t >> 6));  // + 4 a
   auto a5 = [&](int h) {  // u = b0 + R1 (b1 + 4 b2 + 16 b3) reads (a0 + 4 b3 + 16 b2 + 64 b1 + 256 b0)
     const int u = t + 256 * h, r = u / R1;
@@ -278,8 +343,8 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   };
   for (int b = b0; b < b1; ++b) {
     v2f xa[16], xb[16];
-    // this block's lo[Z m0], requested before the prefetch: its wait at the outputs then
-    // leaves the prefetch in flight (the vector-memory counter completes in order)
+    // this block's lo[Z m0]: a uniform address behind a restrict pointer, so a scalar load, off
+    // the vector-memory counter
     const int64_t m0 = (int64_t)P * b;
     const v2f lob = lor[Z * m0];
     {
@@ -305,6 +370,11 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
           xa[i] = load_sample<DT, FLIP>(xrs, L, n);
           xb[i] = load_sample<DT, FLIP>(xrs, L, n + 1);
         }
+        // A run's first and a frame's end blocks only.  Waiting here leaves nothing of this
+        // branch pending where it joins the carried one: without it the carried branch waits
+        // (vmcnt down to 0) for these loads that never ran, which drains the previous block's
+        // output stores on every block.  vmcnt 0, expcnt and lgkmcnt at their maxima.
+        if (!FC_HEAD_DRAIN) __builtin_amdgcn_s_waitcnt(0x0f70);
       }
 #pragma unroll
       for (int i = 0; i < KEEP; ++i) {
@@ -343,10 +413,10 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
     {
       v4f cr[16];
 #pragma unroll
-      for (int i = 0; i < 16; ++i)
-        cr[i] = (FC_KO & 2) ? v4f{1.f, 0.5f, 0.25f, 1.f}
-                : i < HOLD  ? ch[i < HOLD ? i : 0]
-                            : __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(crs, (uint32_t)(16 * t), 4096 * i, 0));
+      for (int j = 0; j < 16; ++j)
+        cr[cix(j)] = (FC_KO & 2) ? v4f{1.f, 0.5f, 0.25f, 1.f}
+                     : j < HOLD  ? ch[j < HOLD ? j : 0]
+                                 : __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(crs, (uint32_t)(16 * t), 4096 * cix(j), 0));
       // one residue pair at a time: its R1 values, DFT each, accumulated into Yf (the whole
       // window's 32 values and C's 32 at once spilled)
       v2f yf[R1];
@@ -376,7 +446,27 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
       for (int q = 0; q < R1; ++q) sl[a1 + 272 * q] = yf[q];
     }
     __syncthreads();
-    // inverse stages 2..4: radix 4 over the digit at stride S, twiddle W_(4S)^(-b k_low)
+    // inverse stages 2..4: radix 4 over the digit at stride S, twiddle W_(4S)^(-b k_low).  They
+    // read and write only the elements of their wave's b0 (t >> 6, + 4 h), so the two exchanges
+    // between them stay in the wave's registers; stage 5 reads every wave's
+#if !FC_INV_LDS
+#pragma unroll
+    for (int h = 0; h < NB; ++h) {
+      v2f v[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) v[a] = sl[a2 + 1088 * h + 68 * a];
+      idft<4>(v);
+      pow_tw<4>(v, ib1);
+      xchg_54(v);
+      idft<4>(v);
+      pow_tw<4>(v, ib2);
+      xchg_32(v);
+      idft<4>(v);
+      pow_tw<4>(v, ib3);
+#pragma unroll
+      for (int a = 0; a < 4; ++a) sl[a4 + 1088 * h + 4 * a] = v[a];
+    }
+#else
     auto istage = [&](int a0, int st, v2f w) {
 #pragma unroll
       for (int h = 0; h < NB; ++h) {
@@ -389,13 +479,12 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
         for (int a = 0; a < 4; ++a) sl[a0 + 1088 * h + st * a] = v[a];
       }
     };
-    // stages 2..4 read and write only the slots of their wave's b0 (t >> 6, + 4 h): the
-    // exchanges between them are wave-local, stage 5 reads every wave's
     istage(a2, 68, ib1);
     stage_sync();
     istage(a3, 17, ib2);
     stage_sync();
     istage(a4, 4, ib3);
+#endif
     __syncthreads();  // (stage 5 inside the wave, outputs R1 apart: 3.11 -> 3.31 ms, r06fc12)
     // stage 5: radix 4 over a0 -> b4; outputs j = u + (M / 4) b4
     {
