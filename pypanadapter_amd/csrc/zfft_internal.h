@@ -1,5 +1,6 @@
-// Internal declarations shared by the plan (zfft_plan.cpp) and the HIP kernels
-// (zfft_kernels.hip).  Not part of the C-ABI.
+// Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp,
+// zfft_waterfall.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
+// (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -124,6 +125,7 @@ struct XaTab {
   alignas(16) float gnb[12][8];
 };
 
+bool xa_build_tables(XaTab &X, int B);  // xa_tables.cpp; false: scan levels too shallow for the poles
 hipError_t launch_xa_stage(const InDesc &in, int n, const float2 *lo, bool mix,
                            float2 *out, int frames, const XaTab *tab, hipStream_t st);
 

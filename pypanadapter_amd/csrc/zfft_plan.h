@@ -1,0 +1,143 @@
+// zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
+// (zfft_plan.cpp, zfft_decim.cpp, zfft_waterfall.cpp).  Not part of the C-ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "zfft.h"
+#include "zfft_internal.h"
+
+namespace zfft {
+
+// A grow-only device buffer, freed with its owner.
+struct DevBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <class T>
+  T *as() const { return static_cast<T *>(p); }
+};
+
+}  // namespace zfft
+
+// One plan = one (N, zoom, W, window, fs, f_lo, scroll) configuration on one device, the
+// analogue of the AppState fields the reference re-reads every frame
+// (pypanadapter_spectrum.py:1492-1497, 2102-2119).  It owns the HIP streams, the LO /
+// window / twiddle tables, a grow-only workspace and the waterfall ring; its buffers are
+// freed by its destructor (zfft_plan_destroy waits for the streams first).
+struct zfft_plan {
+  using DevBuf = zfft::DevBuf;
+  zfft_config cfg{};
+  int K = 0;  // log2(zoom) decimation stages
+  hipStream_t stream = nullptr;
+  std::vector<float> user_window;
+  DevBuf lo, win, tw, in, in2, yf, ping, pong, rows, ring, img, one_row, dec;
+  hipStream_t copy_st = nullptr;            // H2D of the next batch in zfft_process
+  hipEvent_t h2d_ev[2] = {}, comp_ev[2] = {};
+  int64_t lo_len = 0;                       // entries per LO row (0: not built)
+  std::vector<double> lo_freqs;             // set_lo_frames: one LO row per entry (config 4)
+  int lo_per = 1;                           // frames per LO row
+  int lo_first = 0;                         // first frame of the current batch (zfft_process)
+  int win_len = -1;
+  double win_ss = 0.0;
+  int block_override = 0, warm_override = 0;
+  int H = 0, W = 0;
+  int64_t off = 0;
+  bool wf_ready = false;
+  const float *last_row = nullptr;  // device row of the last processed frame
+  bool timing = false;
+  std::vector<hipEvent_t> events;    // one per mark when timing is on
+  std::vector<std::string> mark_names;
+  std::string names_buf;
+  int n_marks = 0;
+  int path = 0;  // 0 auto, 1 exact blocked pipeline, 2 fused interior + edge windows,
+                // 3 XA tiles (all-pole + FIR + half-rate all-pole), 4 PC tiles (polyphase
+                // cascade; zoom 2, 4, 8 and the head of zoom >= 16), 5 PC walk (one workgroup
+                // per frame; zoom 2: the tiles), 6 FC (fast convolution at zoom 4, 8 and the
+                // head; where FC does not fit, as 5) -- zfft_schedule.h choose_schedule
+  int welch = 0;  // 0 auto, 1 one workgroup per frame, 2 four-step
+  DevBuf edge, xk, xa_tab, tws, means, z4, winf;
+  DevBuf pc_tab, pc_edge;  // PC decimator: PcTab; all nine frame-end maps of pc_edge_maps.h
+                           // (floats), uploaded once
+  DevBuf pc_tab4;  // PC zoom 4: PcTab4
+  DevBuf pc_tab2;  // PC zoom 2: PcTab2
+  DevBuf wparts;   // split DIF Welch: partial PSDs (frames x split x n_win floats)
+  DevBuf lo1;      // unit LO table (the blocked passes after the PC head mix with it)
+  int64_t lo1_n = 0;  // entries of lo1 filled (a failed fill leaves it short: refilled next call)
+  int64_t n_quiesce = 0;   // host waits on enqueued work (test hook zfft__plan_quiesce_count)
+  // waterfall rendering: colormap LUT (host copy + device), levels
+  uint8_t lut[256 * 4] = {};
+  bool lut_ready = false;         // lut holds the chosen map (built on first use)
+  bool lut_uploaded = false;      // lut_d holds lut
+  std::string cmap = "Default";
+  double lev_lo = -220.0, lev_hi = -120.0;  // Waterfall.__init__ (S:1593-1598)
+  DevBuf lut_d, rgba, al_hist, al_bins;
+  DevBuf img64;                    // float64 image of the display entries
+  float *row_pin = nullptr;        // page-locked staging of host rows the display kernels read
+  size_t row_pin_cap = 0;          //   in place (no H2D copy command); bytes
+  // Ordering across streams: every call that enqueues work first makes its stream wait for
+  // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
+  // own; the workspaces, tables and the ring are thus used in call order whatever streams the
+  // caller picks, and a synchronous table upload waits for done_ev first.
+  hipEvent_t done_ev = nullptr;
+  hipStream_t done_st = nullptr;
+  bool has_work = false;
+  // the walk's frame-end sums V^T x run on side_st beside it (fork_ev / join_ev), into edge_v
+  hipStream_t side_st = nullptr;
+  hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+  DevBuf edge_v;
+  // FC decimator (path 6): W_1024 twiddles, then one C row per LO frequency; fc_built holds the
+  // f_lo / fs ratios the rows were built for (rebuilt when they change; empty: not built)
+  DevBuf fc_tab;
+  std::vector<double> fc_built;
+};
+
+namespace zfft {
+
+// --- zfft_plan.cpp ---
+int fail(int code, const std::string &msg);  // sets the thread's error message, returns code
+int hip_fail(hipError_t e, const char *where);
+// Timing marks: an event before the first launch and after each launch (or launch group)
+// of a call, with the name of what ran since the previous mark.
+void mark(zfft_plan *p, hipStream_t st, const char *what = "");
+// Order `st` after everything the plan enqueued before (on any stream).
+int use_stream(zfft_plan *p, hipStream_t st);
+// Mark the end of the plan's work enqueued so far on `st`.
+int done_on(zfft_plan *p, hipStream_t st);
+// Wait on the host until the plan's enqueued work is done (before a synchronous upload
+// overwrites a table that work may still read).
+int quiesce(zfft_plan *p);
+int enter(zfft_plan *p);  // null check + hipSetDevice
+int row_length(const zfft_plan *p);  // valid entries per row
+// A NULL stream handle means HIP's default (null) stream, as everywhere in HIP.
+inline hipStream_t pick_stream(zfft_plan *, void *s) { return (hipStream_t)s; }
+
+// --- zfft_decim.cpp ---
+// Stage lengths: n_0 = L, n_{k+1} = ceil(n_k / 2)  (decimate(...)[::2]).
+std::vector<int64_t> stage_lengths(int64_t L, int K);
+int ensure_lo(zfft_plan *p, int64_t L);
+// The plan's K stages on `frames` frames of L samples (n = stage_lengths(L, K)), by the
+// schedule choose_schedule gives; *out = the decimated frames, natural layout.
+int run_decimator(zfft_plan *p, const InDesc &in, int64_t L, int frames,
+                  const std::vector<int64_t> &n, const float2 **out, hipStream_t st);
+
+}  // namespace zfft

@@ -1,6 +1,7 @@
 """Parity at the benchmarked geometry itself ("what's weak" 1): the exact batch
 sizes bench.py times -- cfg2 and cfg3 at F = 4096 frames, cfg5 at F = 2048 (9.8 / 9.7 / 17 GB
-of IQ built on the device by bench.make_frames) -- through the auto schedule (round 6: the PC walk for every one of them), with
+of IQ built on the device by bench.make_frames) -- through the auto schedule (FC for every one of them: zoom 8 from 16 frames per call, zoom 4
+from 32), with
 sampled frames including the first, both sides of a 64-frame boundary, the middle and the
 last two compared against the float64 oracle under the fp32 gate.  Reaches the
 > 4 GiB input offsets and the grid's last workgroup."""

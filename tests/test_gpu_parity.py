@@ -498,18 +498,21 @@ def test_facade_matches_reference_rows():
                                         (16, 384, 262144, "fc"), (16, 512, 262144, "fc"),
                                         (16, 8, 262144, "pc")])
 def test_auto_schedule_by_batch(z, F, L, want):
-    """The automatic decimator schedule follows the measured crossovers (zfft_plan.cpp
-    pc_fits / kPcWalkMinFrames / auto_xa / use_fused, tools/sweep_schedule.py,
-    profiles/r04l): at zoom 8 the PC polyphase cascade for every batch of frames >= 16384
-    samples (one frame per call -- the reference's use -- included), as its walk kernel
-    from 1024 frames per call (round 6: profiles/r06k/sweep_walk.json); zoom >= 16 as PC's
-    first three stages + XA where XA would take
-    the batch and zoom 2's tiles does not (>= 512 frames; zoom 2's tiles below that, then the
-    blocked passes under 16384 samples); at zoom 4 PC's tiles below 512 frames per call and
-    the zoom-4 walk from there; at zoom 2 the tiles below 512, XA from there where XA takes the batch (the
-    tiles, not the blocked passes, for 512-767 frames of > 2^19 samples); for frames < 16384 samples
-    >= 384 frames of <= 2^19 samples (768 of longer ones) the XA tiles and smaller batches the
-    exact blocked passes (the fused interior with edge windows is reached on request only)."""
+    """The automatic decimator schedule follows the measured crossovers (zfft_schedule.cpp
+    choose_schedule; tools/sweep_schedule.py, tools/sweep_walk.py, tools/fc_ab.py).  Frames of
+    >= 16384 samples: at zoom 8 PC's tiles below 16 frames per call (one frame per call -- the
+    reference's use -- included) and FC from 16; at zoom 4 PC's tiles below 32 frames and FC
+    from 32 (the walks, from 1024 / 512 frames, are automatic only where FC does not fit:
+    frames of >= 2^31 bytes); at zoom 2 the tiles below 512 frames, XA from there where XA
+    takes the batch (the tiles, not the blocked passes, for 512-767 frames of > 2^19 samples);
+    zoom >= 16 as the zoom-8 form for the first three stages, then XA where XA would take the
+    batch and zoom 2's tiles do not (>= 512 frames), else zoom 2's tiles and, under 16384
+    samples, the blocked passes.  Frames < 16384 samples: the XA tiles from 384 frames (768
+    for frames > 2^19 samples), the exact blocked passes for smaller batches (the fused
+    interior with edge windows is reached on request only, apart from zoom >= 16 on frames of
+    >= 2^31 bytes).  The
+    chooser's own answer for the same key (zfft__schedule, pinned without a GPU by
+    test_schedule.py) must name what was launched."""
     import torch
     from pypanadapter_amd import ZoomFFT
     dev = torch.device("cuda", 0)
@@ -530,6 +533,17 @@ def test_auto_schedule_by_batch(z, F, L, want):
     assert ("edge_windows" in names) == (want == "fused"), names
     if z == 16:  # the PC head's tail stage: zoom 2's tiles below 512 frames, else XA's
         assert ("xa_stage" in names) == (F >= 512) and names.count("pc_edge") == (1 if F >= 512 else 2), names
+    from test_schedule import schedule
+    rc, name = schedule(z, 0, 0, L, F)
+    head, _, tail = name.partition("+")
+    launched = {"exact": "exact_forward_mix", "fused": "exact_forward_mix", "xa": "xa_stage_mix",
+                "pc2_tiles": "pc_tail", "pc4_tiles": "pc_fir", "pc8_tiles": "pc_fir", "walk4": "pc_walk4",
+                "walk8": "pc_walk", "fc4": "fc_decim", "fc8": "fc_decim"}
+    assert rc == 0 and names[0] == launched[head], (name, names)
+    assert ("edge_windows" in names) == (head == "fused"), (name, names)
+    assert (tail != "") == (z >= 16), (name, names)
+    if head != "xa":
+        assert ("xa_stage" in names) == (tail == "xa"), (name, names)
     del x, rows
     torch.cuda.empty_cache()
 

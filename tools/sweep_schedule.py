@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Re-derive the automatic decimator-schedule crossovers (zfft_plan.cpp auto_xa / use_fused /
+"""Re-derive the automatic decimator-schedule crossovers (zfft_schedule.cpp auto_xa / use_fused /
 pc_fits / kPcWalkMinFrames) from one GPU run: per-call device time of each schedule (path 1
 exact blocked, 2 fused blocked + edge windows, 3 XA tiles, 4 PC polyphase cascade tiles, 5 PC
 walk: one workgroup per frame) over batch sizes, for cfg2-length
 frames (L = 299,008 <= 2^19) and cfg5-length frames (L = 2^20).  Writes a JSON stamped with the kernel-source
-hash; DESIGN.md cites it, and the constants in zfft_plan.cpp are the crossovers it finds.
+hash; DESIGN.md cites it, and the constants in zfft_schedule.cpp are the crossovers it finds.
 usage: python tools/sweep_schedule.py OUT.json"""
 import json
 import os

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Walk crossovers after round 6's walk changes (zfft_plan.cpp kPcWalkMinFrames and the zoom-4
+"""Walk crossovers after round 6's walk changes (zfft_schedule.cpp kPcWalkMinFrames and the zoom-4
 choice between XA, the tiles and the walk): per-call device time (HIP events, median of 5 after
 2 warm calls) of the PC tiles (path 4), the walk (path 5) and XA (path 3, zoom 4 only) over batch
 sizes, zoom 8 at cfg2's and cfg5's frame lengths (N = 4096), zoom 4 at cfg1's (N = 1024).
