@@ -210,7 +210,7 @@ int zfft_plan_timings(zfft_plan *plan, float *ms_out, int32_t max, int32_t *coun
 /* Comma-separated names of the intervals zfft_plan_timings returns (owned by the plan). */
 const char *zfft_plan_timing_names(zfft_plan *plan);
 
-/* Decimator schedule: 0 = automatic -- for zoom 8 and frames of >= 16384 samples 4 below
+/* Decimator schedule (path 0 ... 7): 0 = automatic -- for zoom 8 and frames of >= 16384 samples 4 below
  * 16 frames per call and 6 from there (zoom >= 16: the same for the first three stages;
  * zoom 4: 4 below 32 frames per call and 6 from there; zoom 2: 4 below 512); otherwise 3 for
  * batches of >= 768 frames, or >= 384 frames of <= 2^19
@@ -249,7 +249,16 @@ const char *zfft_plan_timing_names(zfft_plan *plan);
  * filter and the LO's modulation, one inverse DFT per window, one launch with one workgroup
  * per frame (or per run of windows below 1024 frames per call), the frame-end maps as for 5;
  * frames of >= 8192 samples below 2^31 bytes (cfg2's 4096 frames: 2.66 ms against the walk's
- * 4.18; cfg1's: 2.82 against the zoom-4 walk's 4.22).  Path 3
+ * 4.18; cfg1's: 2.82 against the zoom-4 walk's 4.22); 7 = FC wherever a form exists, on request
+ * only: as 6, plus zoom 2 (two residues of 4096 points, the one-stage model truncated at
+ * |k| <= 256, 3840 outputs per window) and, at zoom >= 16, FC launches for the stages after the
+ * head as well (three at a time, then two or one, while a launch's input has >= 16384 samples;
+ * then as 6's tail) -- decimated IQ within 5.4e-7 of the reference's peak at zoom 2 and within
+ * 6.9e-7 / 7.6e-7 at zoom 16 / 64 (measured worst 5.03e-7, 6.43e-7, 7.06e-7 + 7 %,
+ * tests/test_gpu_fc2.py, profiles/r08fc2; 6's tails: 4e-6); cfg2's 4096 frames, ms per step,
+ * automatic / 7: zoom 2 5.17 / 5.27 (FC wins between about 64 and 512 frames per call: 0.88
+ * against 1.17 at 512), zoom 16 3.12 / 3.20, zoom 64 3.37 / 2.96; frames of >= 16384 samples
+ * below 2^31 bytes, outside that as 6.  Path 3
  * needs every stage array below 2^31 bytes per frame; a forced path outside its domain
  * returns ZFFT_EUNSUPPORTED.  All produce the reference's rows within the fp32 parity gate
  * (zfft_plan.cpp auto_xa, use_fused, pc_fits, fc_fits). */

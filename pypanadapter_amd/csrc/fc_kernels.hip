@@ -1,5 +1,7 @@
 // fc_kernels.hip -- "FC", the fast-convolution form of the zoom-8 decimator on gfx950 (host
-// tables: fc_build_table in pc_tables.cpp; design model: tools/fc_model.py).
+// tables: fc_build_table in pc_tables.cpp; design model: tools/fc_model.py), of
+// zoom 4 (four residues of 2048 points) and of zoom 2 (path 7: two residues of 4096 points, the
+// one-stage model truncated at |k| <= 256, 3840 outputs per window).  Zoom 8:
 //
 // The interior of three scipy.signal.decimate(x, 2) (pypanadapter_spectrum.py:2096-2098) is the
 // zero-phase LTI filter G = prod_k |H(z^(2^k))|^2 on the zero-extended frame followed by [::8]
@@ -59,6 +61,9 @@
 #else
 #define FC_RESTRICT __restrict__
 #endif
+#ifndef FC_PF1
+#define FC_PF1 10  // zoom 2, complex64: pairs of the next window requested at the block head
+#endif
 #ifndef FC_HOLD
 #define FC_HOLD (-1)  // diagnostic override of fc_hold for every non-cu8 instantiation
 #endif
@@ -75,14 +80,18 @@ typedef v4f __attribute__((address_space(3))) *LP4;
 template <int Z> struct Geo;
 template <> struct Geo<8> { static constexpr int S = kFcStep, K = kFcK, P = kFcP; };
 template <> struct Geo<4> { static constexpr int S = kFc4Step, K = kFc4K, P = kFc4P; };
+template <> struct Geo<2> { static constexpr int S = kFc2Step, K = kFc2K, P = kFc2P; };
 constexpr int kN = kFcN;
 // LDS: the window as [pos][residue] with 2 pad slots per 32 (conflict-free b128 reads in all
 // three forward passes, tools/fc_model.py layout check); the inverse M points, 1 pad per 16 --
-// its own array at zoom 8 (1024 points), inside the window's at zoom 4 (2048: two arrays would
-// not fit two workgroups per CU)
+// its own array at zoom 8 (1024 points), inside the window's at zoom 4 and 2 (2048 / 4096: two
+// arrays would not fit two workgroups per CU)
 constexpr int kBigSlots = kN + 2 * (kN / 32);
 constexpr int kSmallSlots8 = 1024 + 1024 / 16;
-__device__ __forceinline__ int ps(int i) { return i + (i >> 4); }
+// Zoom 2 pads once more per 256: stage 5's lanes read 256 b0 apart for 16 values of b0 (R1), which
+// 1 per 16 alone leaves on two bank groups (8-way; 4-way at zoom 4's 8 values, 2-way at zoom 8)
+template <int Z>
+__device__ __forceinline__ int ps(int i) { return i + (i >> 4) + (Z == 2 ? i >> 8 : 0); }
 
 // acc + a b (complex) in two VOP3P instructions (cmul2 with the accumulator as the addend)
 __device__ __forceinline__ v2f cmac2(v2f acc, v2f a, v2f b) {
@@ -104,7 +113,7 @@ __device__ __forceinline__ void idft(v2f *v) {
     v[R - b] = s;
   }
 }
-// v[b] *= w^b, b = 1 .. R-1 (R = 4, 8)
+// v[b] *= w^b, b = 1 .. R-1 (R = 4, 8, 16)
 template <int R>
 __device__ __forceinline__ void pow_tw(v2f *v, v2f w);
 template <>
@@ -124,6 +133,27 @@ __device__ __forceinline__ void pow_tw<8>(v2f *v, v2f w) {  // each power from a
   v[5] = cmul2(v[5], cmul2(w4, w));
   v[6] = cmul2(v[6], cmul2(w4, w2));
   v[7] = cmul2(v[7], cmul2(w4, w3));
+}
+
+template <>
+__device__ __forceinline__ void pow_tw<16>(v2f *v, v2f w) {  // each power from at most 4 products
+  const v2f w2 = cmul2(w, w), w4 = cmul2(w2, w2), w8 = cmul2(w4, w4), w3 = cmul2(w2, w);
+  const v2f w5 = cmul2(w4, w), w6 = cmul2(w4, w2), w7 = cmul2(w4, w3);
+  v[1] = cmul2(v[1], w);
+  v[2] = cmul2(v[2], w2);
+  v[3] = cmul2(v[3], w3);
+  v[4] = cmul2(v[4], w4);
+  v[5] = cmul2(v[5], w5);
+  v[6] = cmul2(v[6], w6);
+  v[7] = cmul2(v[7], w7);
+  v[8] = cmul2(v[8], w8);
+  v[9] = cmul2(v[9], cmul2(w8, w));
+  v[10] = cmul2(v[10], cmul2(w8, w2));
+  v[11] = cmul2(v[11], cmul2(w8, w3));
+  v[12] = cmul2(v[12], cmul2(w8, w4));
+  v[13] = cmul2(v[13], cmul2(w8, w5));
+  v[14] = cmul2(v[14], cmul2(w8, w6));
+  v[15] = cmul2(v[15], cmul2(w8, w7));
 }
 
 // Loads through buffer resources: one lane offset VGPR and constant SGPR offsets per load (64-bit
@@ -236,27 +266,32 @@ __device__ __forceinline__ void stage_sync() {
 // How many of a thread's 16 C pairs stay in registers for the whole kernel instead of being
 // re-read from L2 every block: as many as each instantiation holds without spilling at 2 WG/CU
 // (cu8 has no room; against none, complex64 8 at zoom 8: fc_decim 2.62 -> 2.55 ms at cfg2,
-// r06fc10; 6 at zoom 4 and 14 for complex32 beat 4 and 12 by 1.1 / 0.6 % per step, r06fc13)
+// r06fc10; 6 at zoom 4 and 14 for complex32 beat 4 and 12 by 1.1 / 0.6 % per step, r06fc13).
+// Zoom 2 holds none: pass C is one round of 32 values against all 16 pairs, and complex64
+// spills 13-19 registers even so unless part of the prefetch moves behind it (FC_PF1).
 constexpr int fc_hold(int Z, int DT) {
+  if (Z == 2) return 0;
   return DT == kInCU8 ? 0 : DT == kInC64 ? (Z == 8 ? 8 : 6) : 14;
 }
 
 // One workgroup walks blocks [bpc * blockIdx.x, +bpc) of frame blockIdx.y.  tab: W_M^k (k < M),
 // then per LO row (row_stride apart) C as v4f pairs [(Z / 2) k3 + r / 2][t] (r, r + 1) for thread t
-// of pass C.  Needs frames of >= kFcN samples and < 2^31 bytes (launch_fc_decim).
+// of pass C.  Needs frames of >= kFcN samples and < 2^31 bytes (launch_fc_decim); at zoom 2 an
+// LO row of > 4096 entries (the composite below; every caller's frames have >= 16384 samples).
 template <int Z, int DT, int FLIP>
 __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *FC_RESTRICT lo,
                                                          const v2f *FC_RESTRICT tab, int64_t row_stride,
                                                          v2f *FC_RESTRICT out, int64_t nd, int bpc) {
-  constexpr int M = kN / Z;             // per-residue transform: 1024 (zoom 8), 2048 (zoom 4)
+  constexpr int M = kN / Z;             // per-residue transform: 1024 (zoom 8), 2048 (4), 4096 (2)
   constexpr int R1 = M / 256;           // radix of the last forward / first inverse stage
   constexpr int S = Geo<Z>::S, K = Geo<Z>::K, P = Geo<Z>::P;
   constexpr int KEEP = 16 - S;          // a thread's pairs carried into the next window
   constexpr int J0 = K / Z;             // first valid inverse output
   constexpr int NB = M / 1024;          // inverse butterflies per thread in stages 2..5
-  constexpr bool ALIAS = Z == 4;        // the inverse array inside the window's
+  constexpr bool ALIAS = Z != 8;        // the inverse array inside the window's
   static_assert(K == (kN - 512 * S) / 2 && P * Z == 512 * S && K % Z == 0 && KEEP >= 1, "FC block geometry");
   static_assert(J0 + P <= M && J0 < 256 * NB, "FC outputs");
+  static_assert(!ALIAS || M + M / 16 + M / 256 <= kBigSlots, "the inverse array inside the window's");
   __shared__ v4f big4[kBigSlots / 2];
   __shared__ v2f small_[ALIAS ? 2 : kSmallSlots8];
   const LP bl = (LP)big4;
@@ -274,7 +309,8 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   const __amdgpu_buffer_rsrc_t xrs = frame_rsrc<DT>(in, f);
   // pass A: residues of thread t's pairs 2t + 512 i are (2t mod Z, +1), at m = j0 + (M / 16) i;
   // pass B: k1 = t >> 4, j1 = the digit below i2 of the (M / 16)-point remainder
-  const int j0 = t >> (Z == 8 ? 2 : 1), j1 = Z == 8 ? (t >> 2) & 3 : (t >> 1) & 7;
+  constexpr int ZS = Z == 8 ? 2 : Z == 4 ? 1 : 0;  // log2(Z / 2): a thread's pair 2t is position t >> ZS
+  const int j0 = t >> ZS, j1 = (t >> ZS) & (15 >> ZS);
   v2f bA[4], bB[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
@@ -300,28 +336,42 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   // outputs: butterfly u = t + 256 h of stage 5 gives j = u + (M / 4) b4, valid for j in
   // [J0, J0 + P), at output jm = j - J0 of the block; their lo[Z jm] (0 where invalid / past
   // the frame)
-  v2f lj[NB][4];
+  // Zoom 2 has no room for its 16 values: lo is an exact exponential of modulus sqrt 2, so
+  // lo[Z jm] = lo[Z (t + 256 h + M / 4 - J0)] lo[Z (M / 4) (q - 1)] / sqrt 2 -- four per thread
+  // (lt) and four uniform ones (lq; q = 0: the conjugate of q = 2's; divided by the table's
+  // modulus lo[0] = sqrt 2, or 1 for a tail's unit table)
+  constexpr bool LJ = Z != 2;
+  v2f lj[LJ ? NB : 1][4], lt[LJ ? 1 : NB], lq[4];
+  if constexpr (LJ) {
 #pragma unroll
-  for (int h = 0; h < NB; ++h)
+    for (int h = 0; h < NB; ++h)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int jm = t + 256 * h + (M / 4) * q - J0;
-      lj[h][q] = jm >= 0 && jm < P && jm < nd ? lor[Z * jm] : splat(0.f);
-    }
+      for (int q = 0; q < 4; ++q) {
+        const int jm = t + 256 * h + (M / 4) * q - J0;
+        lj[h][q] = jm >= 0 && jm < P && jm < nd ? lor[Z * jm] : splat(0.f);
+      }
+  } else {
+#pragma unroll
+    for (int h = 0; h < NB; ++h) lt[h] = lor[Z * (t + 256 * h + M / 4 - J0)];
+#pragma unroll
+    for (int q = 1; q < 4; ++q) lq[q] = lor[Z * (M / 4) * (q - 1)] * (1.f / lor[0].x);
+    lq[0] = conj(lq[2]);
+  }
   // LDS bases (v2f slots; the pads folded into the constant strides)
   const int aA = 2 * t + 2 * (t >> 4);                 // pb(512 k + 2t) = aA + 544 k
   const int aB = 2 * (t & 15) + 544 * (t >> 4);        // pb(base + 32 i) = aB + 34 i
   const int aC = 544 * (t >> 4) + 34 * (t & 15);       // pair p of pass C: aC + 2 p
-  const int a1 = ps(kp);                               // ps(kp + 256 q) = a1 + 272 q
-  // stages 2..4 (butterfly t + 256 h at +1088 h), stage 5
-  const int a2 = ps((t & 63) + 256 * (t >> 6));                                      // + 68 a
+  constexpr int Q1 = 272 + (Z == 2), H1 = 1088 + 4 * (Z == 2);  // ps(256), ps(1024)
+  const int a1 = ps<Z>(kp);                            // ps(kp + 256 q) = a1 + Q1 q
+  // stages 2..4 (butterfly t + 256 h at + H1 h), stage 5
+  const int a2 = ps<Z>((t & 63) + 256 * (t >> 6));                                      // + 68 a
 #if FC_INV_LDS
-  const int a3 = ps((t & 15) + 64 * ((t >> 4) & 3) + 256 * (t >> 6));               // + 17 a
+  const int a3 = ps<Z>((t & 15) + 64 * ((t >> 4) & 3) + 256 * (t >> 6));               // + 17 a
 #endif
-  const int a4 = ps((t & 3) + 16 * ((t >> 2) & 3) + 64 * ((t >> 4) & 3) + 256 * (t >> 6));  // + 4 a
+  const int a4 = ps<Z>((t & 3) + 16 * ((t >> 2) & 3) + 64 * ((t >> 4) & 3) + 256 * (t >> 6));  // + 4 a
   auto a5 = [&](int h) {  // u = b0 + R1 (b1 + 4 b2 + 16 b3) reads (a0 + 4 b3 + 16 b2 + 64 b1 + 256 b0)
     const int u = t + 256 * h, r = u / R1;
-    return ps(4 * ((r >> 4) & 3) + 16 * ((r >> 2) & 3) + 64 * (r & 3) + 256 * (u % R1));
+    return ps<Z>(4 * ((r >> 4) & 3) + 16 * ((r >> 2) & 3) + 64 * (r & 3) + 256 * (u % R1));
   };
 
   auto wstart = [&](int b) -> int64_t { return (int64_t)(512 * S) * b - K; };
@@ -332,14 +382,23 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   // the next window's new pairs, issued on every block from a window start clamped into the
   // frame (values unused when the next window is not inside it): one unconditional call site,
   // so the wait before their use counts only what was issued after them
+  // Zoom 2, complex64: the first PF1 pairs there and the rest after pass C, whose 32 values and
+  // 16 table pairs leave no room for all 15 (FC_PF1; the others: all at the block head)
+  constexpr int PF1 = Z == 2 && DT == kInC64 ? FC_PF1 : S;
+  uint32_t pvo = 0;
   auto issue_pf = [&](int b) {
     carried = b + 1 < b1 && inside(b + 1);
     int64_t sn = wstart(b + 1);
     sn = sn < 0 ? 0 : (sn > L - kN ? L - kN : sn);
-    const uint32_t vo = pair_vo<DT, FLIP>(L, sn, t);
+    pvo = pair_vo<DT, FLIP>(L, sn, t);
 #pragma unroll
-    for (int i = 0; i < S; ++i)
-      if (!(FC_KO & 1)) pf[i] = load_pair_b<DT, FLIP>(xrs, vo, KEEP + i);
+    for (int i = 0; i < PF1; ++i)
+      if (!(FC_KO & 1)) pf[i] = load_pair_b<DT, FLIP>(xrs, pvo, KEEP + i);
+  };
+  auto issue_pf_rest = [&]() {
+#pragma unroll
+    for (int i = PF1; i < S; ++i)
+      if (!(FC_KO & 1)) pf[i] = load_pair_b<DT, FLIP>(xrs, pvo, KEEP + i);
   };
   for (int b = b0; b < b1; ++b) {
     v2f xa[16], xb[16];
@@ -443,9 +502,10 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
       pow_tw<R1>(yf, ib0);
       if (ALIAS) __syncthreads();  // every pass-C read done before the inverse array overwrites
 #pragma unroll
-      for (int q = 0; q < R1; ++q) sl[a1 + 272 * q] = yf[q];
+      for (int q = 0; q < R1; ++q) sl[a1 + Q1 * q] = yf[q];
     }
     __syncthreads();
+    issue_pf_rest();
     // inverse stages 2..4: radix 4 over the digit at stride S, twiddle W_(4S)^(-b k_low).  They
     // read and write only the elements of their wave's b0 (t >> 6, + 4 h), so the two exchanges
     // between them stay in the wave's registers; stage 5 reads every wave's
@@ -454,7 +514,7 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
     for (int h = 0; h < NB; ++h) {
       v2f v[4];
 #pragma unroll
-      for (int a = 0; a < 4; ++a) v[a] = sl[a2 + 1088 * h + 68 * a];
+      for (int a = 0; a < 4; ++a) v[a] = sl[a2 + H1 * h + 68 * a];
       idft<4>(v);
       pow_tw<4>(v, ib1);
       xchg_54(v);
@@ -464,7 +524,7 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
       idft<4>(v);
       pow_tw<4>(v, ib3);
 #pragma unroll
-      for (int a = 0; a < 4; ++a) sl[a4 + 1088 * h + 4 * a] = v[a];
+      for (int a = 0; a < 4; ++a) sl[a4 + H1 * h + 4 * a] = v[a];
     }
 #else
     auto istage = [&](int a0, int st, v2f w) {
@@ -472,11 +532,11 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
       for (int h = 0; h < NB; ++h) {
         v2f v[4];
 #pragma unroll
-        for (int a = 0; a < 4; ++a) v[a] = sl[a0 + 1088 * h + st * a];
+        for (int a = 0; a < 4; ++a) v[a] = sl[a0 + H1 * h + st * a];
         idft<4>(v);
         pow_tw<4>(v, w);
 #pragma unroll
-        for (int a = 0; a < 4; ++a) sl[a0 + 1088 * h + st * a] = v[a];
+        for (int a = 0; a < 4; ++a) sl[a0 + H1 * h + st * a] = v[a];
       }
     };
     istage(a2, 68, ib1);
@@ -499,8 +559,10 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int jm = t + 256 * h + (M / 4) * q - J0;
-          if (jm >= 0 && jm < P && m0 + jm < nd && !(FC_KO & 4))
-            __builtin_nontemporal_store(cmul2(v[q], cmul2(lob, lj[h][q])), o + jm);
+          if (jm >= 0 && jm < P && m0 + jm < nd && !(FC_KO & 4)) {
+            if constexpr (LJ) __builtin_nontemporal_store(cmul2(v[q], cmul2(lob, lj[h][q])), o + jm);
+            else __builtin_nontemporal_store(cmul2(v[q], cmul2(cmul2(lob, lq[q]), lt[h])), o + jm);
+          }
         }
       }
     }
@@ -510,12 +572,12 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
 
 }  // namespace fc
 
-hipError_t launch_fc_decim(const InDesc &in, const float2 *lo, const float2 *tab, int64_t row_stride,
-                           float2 *out, int64_t nd, int frames, int zoom, hipStream_t st) {
-  if (in.len < kFcN || in.len * (int64_t)in_elem_bytes(in.dtype) >= ((int64_t)1 << 31) ||
-      (zoom != 8 && zoom != 4))
-    return hipErrorInvalidValue;
-  const int P = zoom == 8 ? kFcP : kFc4P;
+namespace {
+
+template <int Z>
+hipError_t fc_launch(const InDesc &in, const float2 *lo, const float2 *tab, int64_t row_stride, float2 *out,
+                     int64_t nd, int frames, hipStream_t st) {
+  constexpr int P = fc::Geo<Z>::P;
   const int nb = (int)((nd + P - 1) / P);
   // about two rounds of the chip's 512 resident workgroups: whole frames from 1024 frames per
   // call, below that each frame split into runs of blocks (a run's first window loads in full)
@@ -524,25 +586,41 @@ hipError_t launch_fc_decim(const InDesc &in, const float2 *lo, const float2 *tab
   const dim3 grid((unsigned)((nb + bpc - 1) / bpc), (unsigned)frames);
   const v2f *l = (const v2f *)lo, *tb = (const v2f *)tab;
   v2f *o = (v2f *)out;
-#define FC_GO(Z, DT, FL) \
+#define FC_GO(DT, FL) \
   hipLaunchKernelGGL((fc::fc_decim_kernel<Z, DT, FL>), grid, dim3(256), 0, st, in, l, tb, row_stride, o, nd, bpc)
-#define FC_DT(Z, FL)                           \
-  do {                                         \
-    if (in.dtype == kInC64) FC_GO(Z, kInC64, FL);        \
-    else if (in.dtype == kInC32H) FC_GO(Z, kInC32H, FL); \
-    else if (in.dtype == kInCU8) FC_GO(Z, kInCU8, FL);   \
-    else FC_GO(Z, kInF32R, FL);                          \
+#define FC_DT(FL)                           \
+  do {                                      \
+    if (in.dtype == kInC64) FC_GO(kInC64, FL);        \
+    else if (in.dtype == kInC32H) FC_GO(kInC32H, FL); \
+    else if (in.dtype == kInCU8) FC_GO(kInCU8, FL);   \
+    else FC_GO(kInF32R, FL);                          \
   } while (0)
-  if (zoom == 8) {
-    if (in.flip) FC_DT(8, 1);
-    else FC_DT(8, 0);
-  } else {
-    if (in.flip) FC_DT(4, 1);
-    else FC_DT(4, 0);
-  }
+  if (in.flip) FC_DT(1);
+  else FC_DT(0);
 #undef FC_DT
 #undef FC_GO
   return hipGetLastError();
 }
+
+}  // namespace
+
+// The zoom-2 instantiations are a translation unit of their own (fc2_kernels.hip includes this
+// file with ZFFT_FC_ZOOM2 set): this one keeps zoom 8 and 4, and the two compile side by side.
+#ifdef ZFFT_FC_ZOOM2
+hipError_t launch_fc2_decim(const InDesc &in, const float2 *lo, const float2 *tab, int64_t row_stride,
+                            float2 *out, int64_t nd, int frames, hipStream_t st) {
+  return fc_launch<2>(in, lo, tab, row_stride, out, nd, frames, st);
+}
+#else
+hipError_t launch_fc_decim(const InDesc &in, const float2 *lo, const float2 *tab, int64_t row_stride,
+                           float2 *out, int64_t nd, int frames, int zoom, hipStream_t st) {
+  if (in.len < kFcN || in.len * (int64_t)in_elem_bytes(in.dtype) >= ((int64_t)1 << 31) ||
+      (zoom != 8 && zoom != 4 && zoom != 2))
+    return hipErrorInvalidValue;
+  if (zoom == 8) return fc_launch<8>(in, lo, tab, row_stride, out, nd, frames, st);
+  if (zoom == 4) return fc_launch<4>(in, lo, tab, row_stride, out, nd, frames, st);
+  return launch_fc2_decim(in, lo, tab, row_stride, out, nd, frames, st);
+}
+#endif
 
 }  // namespace zfft

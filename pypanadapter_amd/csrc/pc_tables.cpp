@@ -396,16 +396,18 @@ void fc_build_twiddles(int M, float2 *tw) {
   }
 }
 
-// Zoom Z (8 or 4): g'[k] = g[k] e^(2 pi i lo_ratio k), |k| <= K (g = the zoom-Z model's input-rate
-// response, model_hz(log2 Z); K = kFcK or kFc4K), placed circularly in N = kFcN; G = its DFT;
+// Zoom Z (8, 4 or 2): g'[k] = g[k] e^(2 pi i lo_ratio k), |k| <= K (g = the zoom-Z model's input-rate
+// response, model_hz(log2 Z); K = kFcK, kFc4K or kFc2K), placed circularly in N = kFcN; G = its DFT;
 // C[k][r] = W_N^(rk) sum_(q < Z) G[k + M q] W_Z^(rq) / (N sqrt 2) for k < M = N / Z (the 1 / sqrt 2:
 // the outputs take lo[Z m] as the composite lo[a] lo[b] = sqrt 2 lo[a + b]).  Stored for pass C's
 // thread t (k' = (t >> 4) + 16 (t & 15), k = k' + 256 k3) as v4f pairs: float2 index
-// (((Z / 2) k3 + r / 2) 256 + t) 2 + r % 2 holds C[k][r].
-bool fc_build_row(int zoom, double lo_ratio, float2 *row) {
-  if (zoom != 8 && zoom != 4) return false;
-  const int N = kFcN, M = kFcN / zoom, K = zoom == 8 ? kFcK : kFc4K, R1 = M / 256;
-  const std::vector<double> &h = model_hz(zoom == 8 ? 3 : 2);
+// (((Z / 2) k3 + r / 2) 256 + t) 2 + r % 2 holds C[k][r].  At Z = 2 a thread's 16 pairs are
+// [k3][t], k3 < 16: one pair (r = 0, 1) per output of pass C's radix 16.  unit_lo drops the
+// 1 / sqrt 2 (a tail of zoom >= 16: unit LO table, lo_ratio 0).
+bool fc_build_row(int zoom, double lo_ratio, float2 *row, bool unit_lo) {
+  if (zoom != 8 && zoom != 4 && zoom != 2) return false;
+  const int N = kFcN, M = kFcN / zoom, K = zoom == 8 ? kFcK : zoom == 4 ? kFc4K : kFc2K, R1 = M / 256;
+  const std::vector<double> &h = model_hz(zoom == 8 ? 3 : zoom == 4 ? 2 : 1);
   if ((int)h.size() < 2 * K + 1) return false;
   const int hc = ((int)h.size() - 1) / 2;
   std::vector<std::complex<double>> g(N, 0.0);
@@ -414,7 +416,7 @@ bool fc_build_row(int zoom, double lo_ratio, float2 *row) {
     g[(k + N) % N] = h[hc + k] * std::polar(1.0, 2.0 * M_PI * turns);
   }
   fft_inplace(g, false);
-  const double s = 1.0 / ((double)N * std::sqrt(2.0));
+  const double s = 1.0 / ((double)N * (unit_lo ? 1.0 : std::sqrt(2.0)));
   for (int t = 0; t < 256; ++t) {
     const int kp = (t >> 4) + 16 * (t & 15);
     for (int k3 = 0; k3 < R1; ++k3) {
@@ -517,12 +519,13 @@ bool pc_edge_map_k(int K, int side, int lmod, PcEdge &out) {
 //   output-rate sections' a1, a2 (41 floats); 15 / 16: zoom-2 left / right map for L mod 2 = arg
 //   built now; 17: the shipped zoom-2 map arg; 18 / 20: the FC twiddles W_M^k of zoom 8 / 4
 //   (M = 1024 / 2048, as floats); 19 / 21: the FC filter row of zoom 8 / 4 for f_lo / fs =
-//   arg / 2^20 (kFcRow complex as floats, kernel order).
+//   arg / 2^20 (kFcRow complex as floats, kernel order); 22 / 23: the same for zoom 2
+//   (M = 4096).
 extern "C" int zfft__pc_tables(int what, int arg, float *out, int cap) {
   using namespace zfft;
-  if (what >= 18 && what <= 21) {
-    const int zoom = what <= 19 ? 8 : 4;
-    const bool tw = what == 18 || what == 20;
+  if (what >= 18 && what <= 23) {
+    const int zoom = what <= 19 ? 8 : what <= 21 ? 4 : 2;
+    const bool tw = (what & 1) == 0;
     const int n = tw ? 2 * (kFcN / zoom) : 2 * kFcRow;
     if (cap < n) return -2;
     if (tw) fc_build_twiddles(kFcN / zoom, (float2 *)out);

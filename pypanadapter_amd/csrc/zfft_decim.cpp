@@ -291,7 +291,7 @@ int ensure_pc(zfft_plan *p) {
   return ZFFT_OK;
 }
 
-// FC tables for the plan's LO rows and FC's zoom (4 or 8): host fp64 build, fc_build_row; one
+// FC tables for the plan's LO rows and FC's zoom (2, 4 or 8): host fp64 build, fc_build_row; one
 // synchronous upload when the LO frequencies change, after the plan's enqueued work.
 int ensure_fc(zfft_plan *p, int zoom) {
   const std::vector<double> freqs = p->lo_freqs.empty() ? std::vector<double>{p->cfg.f_lo} : p->lo_freqs;
@@ -319,6 +319,37 @@ int ensure_fc(zfft_plan *p, int zoom) {
   e = hipMemcpy(p->fc_tab.p, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice);
   if (e != hipSuccess) return hip_fail(e, "FC table upload");
   p->fc_built = ratios;
+  return ZFFT_OK;
+}
+
+// The tables of the FC tails (zoom >= 16, path 7): for launch zoom 8, 4 and 2 the twiddles and
+// the row of f_lo = 0 without the LO's 1 / sqrt 2, at fc_tail_off(zoom); built and uploaded once.
+size_t fc_tail_off(int zoom) {
+  size_t off = 0;
+  for (int z = 8; z > zoom; z >>= 1) off += kFcN / z + kFcRow;
+  return off;
+}
+int ensure_fc_tail(zfft_plan *p) {
+  if (p->fc_tail_tab.p) return ZFFT_OK;
+  std::vector<float2> h;
+  try {
+    h.resize(fc_tail_off(1));
+  } catch (const std::bad_alloc &) {
+    return fail(ZFFT_ENOMEM, "FC table host staging allocation failed");
+  }
+  for (int z = 8; z >= 2; z >>= 1) {
+    float2 *t = h.data() + fc_tail_off(z);
+    fc_build_twiddles(kFcN / z, t);
+    if (!fc_build_row(z, 0.0, t + kFcN / z, true))
+      return fail(ZFFT_EINTERNAL, "FC table: model response unavailable");
+  }
+  DevBuf tab;  // the plan's only once it is whole
+  hipError_t e = tab.ensure(h.size() * sizeof(float2));
+  if (e != hipSuccess) return fail(ZFFT_ENOMEM, "FC table allocation failed");
+  e = hipMemcpy(tab.p, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hip_fail(e, "FC table upload");
+  std::swap(p->fc_tail_tab.p, tab.p);
+  std::swap(p->fc_tail_tab.cap, tab.cap);
   return ZFFT_OK;
 }
 
@@ -421,26 +452,21 @@ class SideFork {
   bool open_ = false;
 };
 
-// The walk (zoom 4 or 8: one launch, y2 -- zoom 4: y1 -- in LDS) or FC in its place
-// (fc_kernels.hip), with the frame-end sums V^T x on the side stream beside it, then out += U v.
-int run_walk(zfft_plan *p, const InDesc &in, int frames, int64_t nd, Head head, hipStream_t st) {
-  const bool fc = head == Head::Fc4 || head == Head::Fc8;
-  const int K = head == Head::Fc4 || head == Head::Walk4 ? 2 : kPcStages;
-  int rc;
-  if (fc && (rc = ensure_fc(p, 1 << K))) return rc;
-  hipError_t e = p->pong.ensure((size_t)frames * nd * sizeof(float2));
-  if (e == hipSuccess) e = p->edge_v.ensure((size_t)frames * 2 * kPcEdgeRank * sizeof(float2));
+// One walk or FC launch over K stages, `in` with LO table `lo` into `out` (nd samples per
+// frame), with the frame-end sums V^T x on the side stream beside it, then out += U v.  fc_tab:
+// the FC table (twiddles, then rows), or null for the walk (K = 2, 3).
+int run_walk_into(zfft_plan *p, const InDesc &in, const float2 *lo, const float2 *fc_tab, int K, float2 *out,
+                  int64_t nd, int frames, const char *name, hipStream_t st) {
+  hipError_t e = p->edge_v.ensure((size_t)frames * 2 * kPcEdgeRank * sizeof(float2));
   if (e != hipSuccess) return fail(ZFFT_ENOMEM, "decimator workspace allocation failed");
   SideFork side(p, st);
   e = side.fork();
   if (e != hipSuccess) return hip_fail(e, "side stream fork");
-  const float2 *lo = p->lo.as<float2>();
-  float2 *out = p->pong.as<float2>();
-  if (fc) e = launch_fc_decim(in, lo, p->fc_tab.as<float2>(), kFcRow, out, nd, frames, 1 << K, st);
+  if (fc_tab) e = launch_fc_decim(in, lo, fc_tab, kFcRow, out, nd, frames, 1 << K, st);
   else if (K == 2) e = launch_pc_walk4(in, lo, out, nd, frames, p->pc_tab4.as<PcTab4>(), st);
   else e = launch_pc_walk(in, lo, out, nd, frames, p->pc_tab.as<PcTab>(), st);
-  if (e != hipSuccess) return hip_fail(e, fc ? "fc_decim launch" : "pc_walk launch");
-  mark(p, st, fc ? "fc_decim" : K == 2 ? "pc_walk4" : "pc_walk");
+  if (e != hipSuccess) return hip_fail(e, fc_tab ? "fc_decim launch" : "pc_walk launch");
+  mark(p, st, name);
   const EdgeMaps m = edge_maps(p, K, in.len);
   // submitted after the walk's launch (before it: the same step time, profiles/r06r)
   e = launch_pc_edge_v(in, lo, p->edge_v.as<float2>(), frames, m.V, m.J, m.r, p->side_st);
@@ -450,6 +476,19 @@ int run_walk(zfft_plan *p, const InDesc &in, int frames, int64_t nd, Head head, 
   if (e != hipSuccess) return hip_fail(e, "pc_edge launch");
   mark(p, st, "pc_edge");
   return ZFFT_OK;
+}
+
+// The walk (zoom 4 or 8: one launch, y2 -- zoom 4: y1 -- in LDS) or FC in its place
+// (fc_kernels.hip; zoom 2 too) on the plan's input, into p->pong.
+int run_walk(zfft_plan *p, const InDesc &in, int frames, int64_t nd, Head head, hipStream_t st) {
+  const bool fc = head == Head::Fc2 || head == Head::Fc4 || head == Head::Fc8;
+  const int K = head == Head::Fc2 ? 1 : head == Head::Fc4 || head == Head::Walk4 ? 2 : kPcStages;
+  int rc;
+  if (fc && (rc = ensure_fc(p, 1 << K))) return rc;
+  hipError_t e = p->pong.ensure((size_t)frames * nd * sizeof(float2));
+  if (e != hipSuccess) return fail(ZFFT_ENOMEM, "decimator workspace allocation failed");
+  return run_walk_into(p, in, p->lo.as<float2>(), fc ? p->fc_tab.as<float2>() : nullptr, K,
+                       p->pong.as<float2>(), nd, frames, fc ? "fc_decim" : K == 2 ? "pc_walk4" : "pc_walk", st);
 }
 
 // One PC / FC form over its stages: n[stages] samples per frame into p->pong.
@@ -467,16 +506,20 @@ int run_pc(zfft_plan *p, const InDesc &in, int frames, int64_t nd, Head head, hi
 // Zoom >= 16: the PC / FC head (3 stages into pong), then stages 3 .. K-1 on its output (no LO
 // mix): XA where XA takes the batch (ping, pong, ... in turn), else zoom 2's tiles and the
 // exact blocked passes (few frames per call, the reference's one: a unit LO table stands for
-// the mix their first pass applies).
+// the mix their first pass applies).  Tail::Fc (path 7): FC launches first, three stages at a
+// time and then the remaining two or one, each while its input has >= 16384 samples, on the
+// unit LO table with the frame-end maps of its own zoom and input length.
 int run_pc_head(zfft_plan *p, const InDesc &in, int frames, const std::vector<int64_t> &n,
                 const Schedule &s, const float2 **out, hipStream_t st) {
   const int64_t n3 = n[kPcStages];
   hipError_t e = hipSuccess;
   if (s.tail != Tail::Xa) {  // ping / pong must not move under a stage's input once the tail sizes them
     const size_t G = (size_t)(frames + 63) / 64 * 64;
-    e = p->pong.ensure(std::max((size_t)frames * n3, p->K > kPcStages + 1 ? G * n[kPcStages + 2] : 0) *
+    // (after FC tail launches any later stage may be the blocked passes' first: both hold n3)
+    const bool fct = s.tail == Tail::Fc;
+    e = p->pong.ensure(std::max((size_t)frames * n3, fct ? G * n3 : p->K > kPcStages + 1 ? G * n[kPcStages + 2] : 0) *
                        sizeof(float2));
-    if (e == hipSuccess) e = p->ping.ensure(G * n[kPcStages + 1] * sizeof(float2));
+    if (e == hipSuccess) e = p->ping.ensure(G * (fct ? n3 : n[kPcStages + 1]) * sizeof(float2));
     if (e == hipSuccess && p->lo1_n < n3) {  // filled length, set only once the fill is enqueued
       e = p->lo1.ensure((size_t)n3 * sizeof(float2));
       if (e == hipSuccess) e = launch_fill_c64(p->lo1.as<float2>(), n3, 1.f, 0.f, st);
@@ -484,15 +527,27 @@ int run_pc_head(zfft_plan *p, const InDesc &in, int frames, const std::vector<in
     }
     if (e != hipSuccess) return fail(ZFFT_ENOMEM, "decimator workspace allocation failed");
   }
-  int rc = run_pc(p, in, frames, n3, s.head, st);
+  int rc = s.tail == Tail::Fc ? ensure_fc_tail(p) : ZFFT_OK;
+  if (rc) return rc;
+  rc = run_pc(p, in, frames, n3, s.head, st);
   if (rc) return rc;
   const float2 *cur = p->pong.as<float2>();
   if (s.tail != Tail::Xa) {
+    int k = kPcStages;
+    if (s.tail == Tail::Fc)
+      for (int z; k < p->K && n[k] >= kPcMinL; k += z) {
+        z = std::min(kPcStages, p->K - k);
+        float2 *dst = cur == p->pong.as<float2>() ? p->ping.as<float2>() : p->pong.as<float2>();
+        const InDesc src{cur, n[k], n[k], kInC64, 0};
+        rc = run_walk_into(p, src, p->lo1.as<float2>(), p->fc_tail_tab.as<float2>() + fc_tail_off(1 << z), z, dst,
+                           n[k + z], frames, "fc_tail", st);
+        if (rc) return rc;
+        cur = dst;
+      }
     // zoom 2's tiles (XA's factorisation, the unit LO table) while a stage's input has >= 16384
     // samples, ping, pong, ... in turn; the blocked passes for the stages after that
-    int k = kPcStages;
     for (; k < p->K && n[k] >= kPcMinL; ++k) {
-      float2 *dst = ((k - kPcStages) & 1) ? p->pong.as<float2>() : p->ping.as<float2>();
+      float2 *dst = cur == p->pong.as<float2>() ? p->ping.as<float2>() : p->pong.as<float2>();
       const InDesc src{cur, n[k], n[k], kInC64, 0};
       e = launch_pc2_tail(src, p->lo1.as<float2>(), dst, n[k + 1], frames, p->pc_tab2.as<PcTab2>(), st);
       if (e != hipSuccess) return hip_fail(e, "pc_tail launch");

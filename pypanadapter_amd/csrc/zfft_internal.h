@@ -268,7 +268,7 @@ hipError_t launch_pc_edge_u(const float2 *v, float2 *out, int64_t n3, int frames
 hipError_t launch_pc_edge(const InDesc &in, const float2 *lo, float2 *out, int64_t n3, int frames,
                           const float *const U[2], const float *const V[2], const int R[2],
                           const int J[2], const int r[2], hipStream_t st);
-// FC (fc_kernels.hip, path 6): the zoom-8 model G as a truncated FIR (|k| <= kFcK) applied by
+// FC (fc_kernels.hip, paths 6 and 7): the zoom-8 model G as a truncated FIR (|k| <= kFcK) applied by
 // overlap-save FFT convolution in 8192-sample windows advancing 512 kFcStep samples (kFcP
 // outputs); the ↓8 is an alias sum in frequency fused with the filter, the LO mix is the
 // filter's modulation.  The table: W_1024^k (k < 1024), then kFcRow entries per LO row.
@@ -283,13 +283,23 @@ constexpr int kFcP = 64 * kFcStep;                 // 832
 constexpr int kFc4Step = 14;
 constexpr int kFc4K = (kFcN - 512 * kFc4Step) / 2;  // 512
 constexpr int kFc4P = 512 * kFc4Step / 4;          // 1792
+// Zoom 2 (path 7): two residues of 4096 points, the one-stage model truncated at |k| <= 256 (tail
+// 1.4e-8 of sum |g|), windows advancing 7680 samples (3840 outputs).
+constexpr int kFc2Step = 15;
+constexpr int kFc2K = (kFcN - 512 * kFc2Step) / 2;  // 256
+constexpr int kFc2P = 512 * kFc2Step / 2;          // 3840
 constexpr int kFcRow = kFcN;  // C[k][r] per LO row, v4f pairs [(zoom / 2) k3 + r / 2][t] (r, r+1)
-// C for zoom 8 or 4 and LO frequency ratio f_lo / fs into row (kFcRow entries); false if the
-// model is unavailable
-bool fc_build_row(int zoom, double lo_ratio, float2 *row);
+// C for zoom 8, 4 or 2 and LO frequency ratio f_lo / fs into row (kFcRow entries); false if the
+// model is unavailable.  unit_lo: without the 1 / sqrt 2 that pairs with the LO table's sqrt 2
+// (the FC tails of zoom >= 16 run on a unit LO table).
+bool fc_build_row(int zoom, double lo_ratio, float2 *row, bool unit_lo = false);
 void fc_build_twiddles(int M, float2 *tw);         // W_M^k, k < M (M = kFcN / zoom)
+// zoom 8, 4 or 2; lo: the LO table of the frames (lo[0] real: sqrt 2, or 1 with a unit_lo row)
 hipError_t launch_fc_decim(const InDesc &in, const float2 *lo, const float2 *tab, int64_t row_stride,
                            float2 *out, int64_t nd, int frames, int zoom, hipStream_t st);
+// zoom 2 (fc2_kernels.hip; launch_fc_decim checks the frame and calls it)
+hipError_t launch_fc2_decim(const InDesc &in, const float2 *lo, const float2 *tab, int64_t row_stride,
+                            float2 *out, int64_t nd, int frames, hipStream_t st);
 
 struct WelchGeom {
   int n_fft, log2n;

@@ -454,9 +454,10 @@ int zfft_plan_timing(zfft_plan *p, int32_t enable) {
 }
 
 int zfft_plan_path(zfft_plan *p, int32_t path) {
-  if (!p || path < 0 || path > 6)
+  if (!p || path < 0 || path > 7)
     return fail(ZFFT_EINVAL, "path must be 0 (auto), 1 (exact), 2 (fused), 3 (XA tiles), 4 (PC "
-                             "tiles), 5 (PC walk) or 6 (FC at zoom 8, else as 5)");
+                             "tiles), 5 (PC walk), 6 (FC at zoom 8 and 4, else as 5) or 7 (FC at "
+                             "zoom 2 and for the tails of zoom >= 16 too, else as 6)");
   p->path = path;
   return ZFFT_OK;
 }

@@ -105,10 +105,13 @@ struct zfft_plan {
   hipStream_t side_st = nullptr;
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;
   DevBuf edge_v;
-  // FC decimator (path 6): W_1024 twiddles, then one C row per LO frequency; fc_built holds the
+  // FC decimator (paths 6, 7): W_M twiddles (M = 8192 / the head's zoom), then one C row per LO frequency; fc_built holds the
   // f_lo / fs ratios the rows were built for (rebuilt when they change; empty: not built)
   DevBuf fc_tab;
   std::vector<double> fc_built;
+  // FC tails of zoom >= 16 (path 7): per launch zoom 8, 4, 2 the twiddles W_M^k and one row at
+  // f_lo = 0 for the unit LO table, one after another; uploaded once
+  DevBuf fc_tail_tab;
 };
 
 namespace zfft {

@@ -97,10 +97,10 @@ constexpr Schedule refused(const char *why) { return {ZFFT_EUNSUPPORTED, Head::E
 // kFcMinFrames frames per call, FC from there) is the fastest schedule wherever it applies,
 // from one frame per call (the reference's use: 0.053 against 0.37 ms for path 1) to full
 // batches (4096 frames: FC 3.44 against the walk's 4.69 ms) -- tools/sweep_schedule.py,
-// profiles/r04l; tools/fc_ab.py, profiles/r06fc3.  FC in the walk's place on request (6) and
-// automatic from kFcMinFrames; a forced 6 outside FC's domain runs the walk.
+// profiles/r04l; tools/fc_ab.py, profiles/r06fc3.  FC in the walk's place on request (6, 7) and
+// automatic from kFcMinFrames; a forced 6 or 7 outside FC's domain runs the walk.
 Head pc8_form(const SchedKey &k) {
-  if (fc_fits(k) && (k.path == 6 || (k.path == 0 && k.frames >= kFcMinFrames))) return Head::Fc8;
+  if (fc_fits(k) && (k.path >= 6 || (k.path == 0 && k.frames >= kFcMinFrames))) return Head::Fc8;
   if (k.path >= 5 || (k.path == 0 && k.frames >= kPcWalkMinFrames)) return Head::Walk8;
   return Head::Pc8Tiles;
 }
@@ -123,13 +123,15 @@ Schedule choose_schedule(const SchedKey &k) {
   // the tiles hand a batch over to XA only where XA takes it (auto_xa: from 768 frames of
   // > 2^19 samples), never to the blocked passes, which lose to the tiles at every batch
   const bool xa_auto = auto_xa(k.frames, k.L) && xa_fits(k);
-  // zoom 2: the tiles on request (paths 4, 5, 6) and automatic below 512 frames per call
+  // zoom 2: FC on request (path 7) where it fits; the tiles on request (paths 4, 5, 6; 7 outside
+  // FC's domain) and automatic below 512 frames per call
+  if (pc2_fits(k) && k.path == 7 && fc_fits(k)) return ok(Head::Fc2, 1);
   if (pc2_fits(k) && (k.path >= 4 || (k.path == 0 && (k.frames < kPc2TilesMaxFrames || !xa_auto))))
     return ok(Head::Pc2Tiles, 1);
   // zoom 4: the tiles below 32 frames per call, FC from there (the walk from 512 where FC
   // does not fit); all on request too
   if (pc4_fits(k) && pc_path) {
-    if (fc_fits(k) && (k.path == 6 || (k.path == 0 && k.frames >= kFc4MinFrames))) return ok(Head::Fc4, 2);
+    if (fc_fits(k) && (k.path >= 6 || (k.path == 0 && k.frames >= kFc4MinFrames))) return ok(Head::Fc4, 2);
     if (k.path >= 5 || (k.path == 0 && k.frames >= kPc4WalkMinFrames)) return ok(Head::Walk4, 2);
     return ok(Head::Pc4Tiles, 2);
   }
@@ -140,7 +142,11 @@ Schedule choose_schedule(const SchedKey &k) {
   if (pc_head_fits(k) && (k.path >= 4 || (k.path == 0 && xa_fits(k)))) {
     const int64_t n3 = (k.L + 7) >> kSchedPcStages;  // the head's output length
     const bool xa_tail = auto_xa(k.frames, n3) && !(k.frames < kPc2TilesMaxFrames && n3 >= kPcMinL);
-    return ok(pc8_form(k), kSchedPcStages, xa_tail ? Tail::Xa : Tail::Pc2TilesThenExact);
+    const Head head = pc8_form(k);
+    // path 7: FC for the stages after an FC head too, while the head's output is long enough
+    // for an FC launch (complex64 of n3 <= L / 8 samples: below 2^31 bytes wherever the head fits)
+    if (k.path == 7 && head == Head::Fc8 && n3 >= kPcMinL) return ok(head, kSchedPcStages, Tail::Fc);
+    return ok(head, kSchedPcStages, xa_tail ? Tail::Xa : Tail::Pc2TilesThenExact);
   }
   if (k.path == 3 || (k.path == 0 && xa_auto)) return ok(Head::Xa, k.K);
   if (use_fused(k)) return ok(Head::Fused, k.K);
@@ -156,12 +162,12 @@ bool batches_keep_xa(const SchedKey &whole) {
 const char *schedule_name(const Schedule &s) {
   if (s.rc != ZFFT_OK) return "unsupported";
   if (s.head_stages == 0) return "none";
-#define ZFFT_SCHED_ROW(h) {h, h "+xa", h "+pc2_exact"}
-  static const char *const names[10][3] = {
+#define ZFFT_SCHED_ROW(h) {h, h "+xa", h "+pc2_exact", h "+fc"}
+  static const char *const names[11][4] = {
       ZFFT_SCHED_ROW("exact"),     ZFFT_SCHED_ROW("fused"),     ZFFT_SCHED_ROW("xa"),
       ZFFT_SCHED_ROW("pc2_tiles"), ZFFT_SCHED_ROW("pc4_tiles"), ZFFT_SCHED_ROW("pc8_tiles"),
       ZFFT_SCHED_ROW("walk4"),     ZFFT_SCHED_ROW("walk8"),     ZFFT_SCHED_ROW("fc4"),
-      ZFFT_SCHED_ROW("fc8")};
+      ZFFT_SCHED_ROW("fc8"),       ZFFT_SCHED_ROW("fc2")};
 #undef ZFFT_SCHED_ROW
   return names[(int)s.head][(int)s.tail];
 }

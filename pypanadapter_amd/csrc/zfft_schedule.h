@@ -11,16 +11,18 @@ namespace zfft {
 struct SchedKey {
   int K;           // log2(zoom) decimation stages (0: zoom 1, no decimator)
   int elem_bytes;  // bytes per input sample (in_elem_bytes of the plan's in_dtype)
-  int path;        // zfft_plan_path: 0 auto, 1 .. 6 forced
+  int path;        // zfft_plan_path: 0 auto, 1 .. 7 forced
   int64_t L;       // samples per frame
   int frames;      // frames per call
 };
 
 // What runs the first stages (all K of them unless a tail follows).
-enum class Head { Exact, Fused, Xa, Pc2Tiles, Pc4Tiles, Pc8Tiles, Walk4, Walk8, Fc4, Fc8 };
+enum class Head { Exact, Fused, Xa, Pc2Tiles, Pc4Tiles, Pc8Tiles, Walk4, Walk8, Fc4, Fc8, Fc2 };
 // Zoom >= 16 after a three-stage PC / FC head: XA stages, or zoom 2's tiles while a stage's
-// input has >= 16384 samples and the exact blocked passes after that.
-enum class Tail { None, Xa, Pc2TilesThenExact };
+// input has >= 16384 samples and the exact blocked passes after that, or (path 7) FC launches
+// of three, two or one stages while a launch's input has >= 16384 samples and the former after
+// that.
+enum class Tail { None, Xa, Pc2TilesThenExact, Fc };
 
 struct Schedule {
   int rc;           // ZFFT_OK or ZFFT_EUNSUPPORTED
@@ -40,7 +42,7 @@ constexpr int kEdge = 384;
 inline int64_t edge_window(int K) { return ((int64_t)1 << K) * (kEdge + 640); }
 
 Schedule choose_schedule(const SchedKey &k);
-// "fc8", "pc8_tiles+xa", "walk8+pc2_exact", ...; "none" at zoom 1, "unsupported" when refused
+// "fc8", "pc8_tiles+xa", "walk8+pc2_exact", "fc8+fc", ...; "none" at zoom 1, "unsupported" when refused
 const char *schedule_name(const Schedule &s);
 
 // Frames per call from which XA takes frames of L samples (where nothing faster applies).

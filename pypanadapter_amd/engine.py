@@ -125,7 +125,14 @@ class ZoomFFT:
         zoom 4 is its tiles, automatic below 1024 frames per call; at zoom 2, 4 and 5 are
         one-stage tiles in XA's factorisation, automatic below 512).  At zoom
         >= 16, 4 / 5 run PC for the first three stages and XA for the rest; automatic wherever
-        XA would take the batch."""
+        XA would take the batch.  6 FC, fast convolution in 8192-sample windows (zoom 8, zoom 4
+        and the head of zoom >= 16; automatic from 16 / 32 frames per call; elsewhere as 5).
+        7 FC wherever a form exists, on request only: as 6, plus zoom 2 (the one-stage model
+        truncated at |k| <= 256, within 5.4e-7 of the float64 reference's decimated IQ) and, at
+        zoom >= 16, FC launches for the stages after the head too while their input has
+        >= 16384 samples (zoom 16 / 64 within 6.9e-7 / 7.6e-7 against 4e-6 with the other
+        tails); frames of >= 16384 samples below 2^31 bytes, outside that as 6.  Times:
+        DESIGN §3.9.1, profiles/r08fc2."""
         check(self.lib.zfft_plan_path(self._plan, int(path)), "zfft_plan_path")
 
     def set_welch(self, mode: int) -> None:

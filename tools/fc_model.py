@@ -93,6 +93,15 @@ def main():
         tail = np.abs(g[c + K + 1:]).sum() * 2 / s
         print(f"K {K:5d}: tail sum / sum|g| {tail:.2e};  VALU/sample N=8192 "
               f"{valu_estimate(8192, K):.1f}  N=16384 {valu_estimate(16384, K):.1f}")
+    # zoom 2 (path 7, fc_decim_kernel<2>): the one-stage response |H(z)|^2 alone; K = 256 fits
+    # 8192-sample windows advancing 512 * 15 samples
+    imp = np.zeros(6000)
+    imp[0] = 1
+    h = ss.sosfilt(SOS, imp)
+    g2 = np.convolve(h, h[::-1])
+    c2, s2 = len(g2) // 2, np.abs(g2).sum()
+    for K in (128, 192, 256, 384):
+        print(f"zoom 2 K {K:4d}: tail sum / sum|g| {np.abs(g2[c2 + K + 1:]).sum() * 2 / s2:.2e}")
     rng = np.random.default_rng(7)
     L = 299008
     x = (rng.standard_normal(L) + 1j * rng.standard_normal(L)) / np.sqrt(2)
