@@ -25,7 +25,9 @@
 // exchanges of the 8192-point window plus three small ones of the 1024-point inverse per block
 // (inverse stages 2..4 exchange between a wave's lanes in registers).
 #include <algorithm>
+#include <type_traits>
 
+#include "fc_prefetch_plan.h"
 #include "zfft_device.h"
 #include "zfft_fft.h"
 #include "zfft_pairs.h"
@@ -61,8 +63,9 @@
 #else
 #define FC_RESTRICT __restrict__
 #endif
-#ifndef FC_PF1
-#define FC_PF1 10  // zoom 2, complex64: pairs of the next window requested at the block head
+// FC_PARENT, FC_PF_SPREAD, FC_PF1: fc_prefetch_plan.h (the request schedule of the next window)
+#ifndef FC_OUT_BUF
+#define FC_OUT_BUF (!FC_PARENT)  // 0 = the outputs stored under a lane condition, through plain pointers
 #endif
 #ifndef FC_HOLD
 #define FC_HOLD (-1)  // diagnostic override of fc_hold for every non-cu8 instantiation
@@ -269,9 +272,15 @@ __device__ __forceinline__ void stage_sync() {
 // r06fc10; 6 at zoom 4 and 14 for complex32 beat 4 and 12 by 1.1 / 0.6 % per step, r06fc13).
 // Zoom 2 holds none: pass C is one round of 32 values against all 16 pairs, and complex64
 // spills 13-19 registers even so unless part of the prefetch moves behind it (FC_PF1).
+// With the next window requested in pieces (fc_prefetch_plan.h) its registers fill as the block
+// goes instead of all being live from the block head, and the room goes to the table: all 16
+// pairs, so pass C issues no load at all and nothing in the block loop waits for the table
+// (with the spread: cfg2 -3.9 % per step, cfg1 -5.1 %, complex32 -3.3 %, profiles/r09fcpf); 13
+// for complex64 at zoom 4 (14 spills 2 registers).  The values of before where the requests are not spread (cu8, FC_PARENT).
 constexpr int fc_hold(int Z, int DT) {
   if (Z == 2) return 0;
-  return DT == kInCU8 ? 0 : DT == kInC64 ? (Z == 8 ? 8 : 6) : 14;
+  if (!pf_spread(Z, DT)) return DT == kInCU8 ? 0 : DT == kInC64 ? (Z == 8 ? 8 : 6) : 14;
+  return DT == kInC64 && Z == 4 ? 13 : 16;
 }
 
 // One workgroup walks blocks [bpc * blockIdx.x, +bpc) of frame blockIdx.y.  tab: W_M^k (k < M),
@@ -380,25 +389,38 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   v2f ka[KEEP], kb[KEEP];      // this window's pairs S .. 15 = the next window's 0 .. KEEP-1
   bool carried = false;        // ka, kb and pf hold this block's window
   // the next window's new pairs, issued on every block from a window start clamped into the
-  // frame (values unused when the next window is not inside it): one unconditional call site,
-  // so the wait before their use counts only what was issued after them
-  // Zoom 2, complex64: the first PF1 pairs there and the rest after pass C, whose 32 values and
-  // 16 table pairs leave no room for all 15 (FC_PF1; the others: all at the block head)
-  constexpr int PF1 = Z == 2 && DT == kInC64 ? FC_PF1 : S;
+  // frame (values unused when the next window is not inside it): unconditional call sites, so
+  // the wait before their use counts only what was issued after them.
+  // They are requested in groups at up to five points of the block (fc_prefetch_plan.h) and not
+  // in one burst at its head: a wave's 13 requests back to back wait on the memory pipeline's
+  // back-pressure wherever they stand (~2,100 cycles of a block when all follow pass C, the
+  // stamps of profiles/r09fcpf), 4 + 4 + 5 mostly do not, and the registers of the next window
+  // fill as the block goes, which is the room in which fc_hold keeps the whole filter table
+  // (cfg2: -2.7 % per step at the hold of before, -3.9 % with it).  The scheduling barriers
+  // keep each group where it is written (the compiler otherwise merges the groups of the head
+  // and of pass A into one burst).  Zoom 2, complex64: the first FC_PF1 pairs at the head and
+  // the rest after pass C, whose 32 values and 16 table pairs leave no room for all 15.
+  static_assert(kPfC64 == kInC64 && kPfC32H == kInC32H && kPfCU8 == kInCU8 && kPfF32R == kInF32R, "formats");
+  static_assert(pf_step(Z) == S && pf_valid(Z, DT, FLIP), "the plan requests each new pair once");
+  constexpr bool PIN = Z != 2 && pf_count(Z, DT, FLIP, kPfHead) != S;
   uint32_t pvo = 0;
+  auto pf_group = [&](auto point) {
+    constexpr int g = decltype(point)::value;
+    constexpr int first = pf_first(Z, DT, FLIP, g), n = pf_count(Z, DT, FLIP, g);
+    if constexpr (n > 0 && !(FC_KO & 1)) {
+      if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = first; i < first + n; ++i) pf[i] = load_pair_b<DT, FLIP>(xrs, pvo, KEEP + i);
+      if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+#define FC_PF_AT(point) pf_group(std::integral_constant<int, point>{})
   auto issue_pf = [&](int b) {
     carried = b + 1 < b1 && inside(b + 1);
     int64_t sn = wstart(b + 1);
     sn = sn < 0 ? 0 : (sn > L - kN ? L - kN : sn);
     pvo = pair_vo<DT, FLIP>(L, sn, t);
-#pragma unroll
-    for (int i = 0; i < PF1; ++i)
-      if (!(FC_KO & 1)) pf[i] = load_pair_b<DT, FLIP>(xrs, pvo, KEEP + i);
-  };
-  auto issue_pf_rest = [&]() {
-#pragma unroll
-    for (int i = PF1; i < S; ++i)
-      if (!(FC_KO & 1)) pf[i] = load_pair_b<DT, FLIP>(xrs, pvo, KEEP + i);
+    FC_PF_AT(kPfHead);
   };
   for (int b = b0; b < b1; ++b) {
     v2f xa[16], xb[16];
@@ -448,6 +470,7 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
     apply_powers2(xa, xb, bA);
 #pragma unroll
     for (int k = 0; k < 16; ++k) *(LP4)(bl + aA + 544 * k) = cat(xa[k], xb[k]);
+    FC_PF_AT(kPfAfterA);
     __syncthreads();
     // pass B: ((M / 16) k1 + j1 + (M / 256) i2) -> DFT16 over i2 -> k2, twiddle
     // W_(M / 16)^(j1 k2), in place
@@ -465,6 +488,7 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
 #pragma unroll
       for (int k = 0; k < 16; ++k) *(LP4)(bl + aB + 34 * k) = cat(ya[k], yb[k]);
     }
+    FC_PF_AT(kPfAfterB);
     __syncthreads();
     // pass C: ((M / 16) k1 + R1 k2 + j1, r) for all j1 < R1, r < Z -> DFT_R1 over j1 -> k3;
     // Yf = sum_r A_r C; inverse stage 1 (radix R1 over k3 -> b0, twiddle W_M^(-b0 kp)) to
@@ -497,6 +521,7 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
           const v4f c = cr[Z / 2 * k + rp];
           yf[k] = cmac2(cmac2(yf[k], ea[k], lo2(c)), eb[k], hi2(c));
         }
+        if (rp == Z / 4 - 1) FC_PF_AT(kPfMidC);
       }
       idft<R1>(yf);
       pow_tw<R1>(yf, ib0);
@@ -505,7 +530,7 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
       for (int q = 0; q < R1; ++q) sl[a1 + Q1 * q] = yf[q];
     }
     __syncthreads();
-    issue_pf_rest();
+    FC_PF_AT(kPfAfterC);
     // inverse stages 2..4: radix 4 over the digit at stride S, twiddle W_(4S)^(-b k_low).  They
     // read and write only the elements of their wave's b0 (t >> 6, + 4 h), so the two exchanges
     // between them stay in the wave's registers; stage 5 reads every wave's
@@ -549,6 +574,16 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
     // stage 5: radix 4 over a0 -> b4; outputs j = u + (M / 4) b4
     {
       v2f *o = out + f * nd + m0;
+      // Zoom 8 and 4 (not cu8) store through a buffer resource over this block's outputs inside the frame,
+      // every lane, every time: a lane without a valid output gives an offset past the resource's
+      // end, which the range check drops (as the window's loads outside the frame return 0).
+      // Four straight-line stores the compiler can count, so its wait for the last prefetched
+      // pair at the next block's head leaves them in flight; around stores under a lane
+      // condition it waits for everything.
+      constexpr bool OBUF = FC_OUT_BUF && Z != 2 && DT != kInCU8;  // the instantiations that spread
+      const int64_t left = nd - m0;
+      const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
+          (void *)o, (short)0, OBUF ? 8 * (int)(left < P ? left : P) : 0, kBufFlags);
 #pragma unroll
       for (int h = 0; h < NB; ++h) {
         const int i5 = a5(h);
@@ -559,7 +594,13 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int jm = t + 256 * h + (M / 4) * q - J0;
-          if (jm >= 0 && jm < P && m0 + jm < nd && !(FC_KO & 4)) {
+          if constexpr (OBUF) {
+            typedef unsigned u2 __attribute__((ext_vector_type(2)));
+            const v2f y = cmul2(v[q], cmul2(lob, lj[h][q]));
+            if (!(FC_KO & 4))  // non-temporal, as the pointer stores
+              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, y), ors,
+                                                    jm >= 0 ? 8u * (uint32_t)jm : 0x80000000u, 0, 2);
+          } else if (jm >= 0 && jm < P && m0 + jm < nd && !(FC_KO & 4)) {
             if constexpr (LJ) __builtin_nontemporal_store(cmul2(v[q], cmul2(lob, lj[h][q])), o + jm);
             else __builtin_nontemporal_store(cmul2(v[q], cmul2(cmul2(lob, lq[q]), lt[h])), o + jm);
           }
@@ -568,6 +609,7 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
     }
     if (ALIAS) __syncthreads();  // stage-5 reads done before the next window's pass-A stores
   }
+#undef FC_PF_AT
 }
 
 }  // namespace fc

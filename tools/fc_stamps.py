@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-phase cycle shares of the FC kernel (path 6) from a -DFC_STAMPS=1 build of
-fc_kernels.hip with tools/patches/fc_stamps_r07.patch applied (run with ZFFT_LIB_PATH=<that lib>;
-fc_stamps_r06.patch is the same for the sources before the inverse's lane exchanges).
+fc_kernels.hip with tools/patches/fc_stamps_r09.patch applied (run with ZFFT_LIB_PATH=<that lib>;
+fc_stamps_r07.patch is the same for the sources before the spread prefetch, fc_stamps_r06.patch
+for those before the inverse's lane exchanges).
 Diagnostic only: read the SHARES (s_memtime cycles per wave and block, each barrier's wait in the
 phase it ends), not the run time of this build.  usage: fc_stamps.py [frames]"""
 import ctypes
