@@ -280,6 +280,30 @@ int zfft_plan_set_lo_frames(zfft_plan *plan, const double *f_lo, int32_t n, int3
  * Same rows within the parity gate; diagnostics / A-B only. */
 int zfft_plan_welch(zfft_plan *plan, int32_t mode);
 
+/* Welch detector: how a frame's segments combine into its row.  With P_s[k] = |X_s,k|^2 /
+ * (fs * sum(w^2)) the density of segment s (constant detrend, periodic window, 50 % overlap,
+ * fs the original rate; one-sided rows: the doubled bins, per segment),
+ *   ZFFT_AVG_MEAN    mean_s P_s[k] -- scipy.signal.welch's default and the reference's call;
+ *                    the plan's default, the same kernels and rows as without this call;
+ *   ZFFT_AVG_MEDIAN  median_s P_s[k] / bias(nseg) -- scipy.signal.welch(average='median'):
+ *                    numpy's median (even nseg: the mean of the two middle values), bias(n) =
+ *                    1 + sum_{i=1..(n-1)/2} (1/(2i+1) - 1/(2i)), computed in double on the host.
+ *                    An impulse that sits in a few segments leaves the row where it was;
+ *   ZFFT_AVG_MAX     max_s P_s[k], no bias: the peak (max-hold) detector over the frame, for
+ *                    transmissions shorter than it (the mean dilutes them by nseg).
+ * Rows stay 20*log10 of the fftshift-cropped bins, zfft_plan_row_length long; a zero bin gives
+ * -inf, a NaN in any segment NaN.  A frame with one segment (nseg 1, e.g. the short-input
+ * branch L_d < n_fft) gives the same row in all three (bias(1) = 1).  Valid wherever mean is:
+ * every n_fft, both zfft_plan_welch forms, any number of frames and segments.  The mode holds
+ * for every later zfft_process* / zfft_ring_process call until it is changed; any other value
+ * is ZFFT_EINVAL.  Median and max keep every segment's bins in a device scratch (nseg * n_win
+ * floats per frame; the frames of a call go in chunks of at most 1 GiB of it, one frame at
+ * least) and reduce them with a second kernel: with zfft_plan_timing they report
+ * "welch_segs" / "welch4_segs" then "welch_select" per chunk in place of "welch_rows" /
+ * "welch4". */
+enum zfft_average { ZFFT_AVG_MEAN = 0, ZFFT_AVG_MEDIAN = 1, ZFFT_AVG_MAX = 2 };
+int zfft_plan_average(zfft_plan *plan, int32_t mode);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

@@ -323,14 +323,29 @@ struct WelchGeom {
 // N = 4096), at least two segments each; 1 for full batches.
 int welch_dif_split(int n_fft, int nseg, int frames);
 
+// segs (median / max detectors, zfft_plan_average): instead of the dB rows, every segment's
+// scaled linear bins into rows[(f nseg + s) n_win + j] (g.scale then without 1/nseg; the split
+// form writes them at their absolute s and needs neither g.parts nor a second launch).
 hipError_t launch_welch_rows(const float2 *x, int64_t len, const float *win, const float2 *tw,
-                             const WelchGeom &g, float *rows, int frames, hipStream_t st);
+                             const WelchGeom &g, float *rows, int frames, hipStream_t st,
+                             bool segs = false);
 
 // Four-step Welch for N = N1 * 256, 16 <= N1 <= 256: means (frames*nseg), z (frames*nseg*N)
-// workspaces; tws = W_256^m (256) ++ W_N1^m (N1).
+// workspaces; tws = W_256^m (256) ++ W_N1^m (N1).  seg_out: launch_welch_rows' segs.
 hipError_t launch_welch4(const float2 *x, int64_t len, const float *win, const float2 *tw,
                          const float2 *tws, const float2 *winf, const WelchGeom &g, float2 *means,
-                         float2 *z, float *rows, int frames, hipStream_t st);
+                         float2 *z, float *rows, int frames, hipStream_t st, bool seg_out = false);
+
+// The detector over a frame's segments: rows[f n_win + j] = 20 log10(median_s / bias) (mode 1,
+// numpy's median; inv_bias = 1 / median_bias(nseg)) or 20 log10(max_s) (mode 2) of
+// seg[(f nseg + s) n_win + j], j < row_len.
+struct WelchSelect {
+  int nseg, n_win, row_len;
+  int mode;
+  float inv_bias;
+  int jblocks = 0;  // (set by the launch) workgroups per frame
+};
+hipError_t launch_welch_select(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st);
 
 hipError_t launch_waterfall_init(float *ring, int H, int W, hipStream_t st);
 hipError_t launch_waterfall_push(float *ring, int H, int W, const float *rows,

@@ -514,7 +514,10 @@ __device__ __forceinline__ int stockham_out_index(int t, int N, int Ns, int i) {
 // pass; then radix-16 Stockham passes through LDS; the last pass accumulates |X|^2 in
 // registers for every bin the thread owns.  The next segment's loads are issued before
 // the current FFT (register prefetch).  Finally: density scale, fftshift crop, 20 log10.
-template <int R0, bool PF, int MAXT>  // PF: register prefetch of the next segment
+// SEG (median / max detectors, zfft_plan_average): nothing is summed; segment s's kept bins
+// go, scaled (g.scale = the density scale without 1/nseg), to rows[(f nseg + s) n_win + j] --
+// the scratch welch_select_kernel reduces.
+template <int R0, bool PF, int MAXT, bool SEG = false>  // PF: register prefetch of the next segment
 __global__ __launch_bounds__(MAXT, 1) void welch_rows_kernel(const v2f *__restrict__ x, int64_t len,
                                                           const float *__restrict__ win,
                                                           const v2f *__restrict__ tw,
@@ -593,11 +596,23 @@ __global__ __launch_bounds__(MAXT, 1) void welch_rows_kernel(const v2f *__restri
       Ns *= 16;
     }
     if (act) {
+      if constexpr (SEG) {
+        float *__restrict__ srow = rows + ((int64_t)f * g.nseg + s) * g.n_win;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = fmaf(v[i].x, v[i].x, fmaf(v[i].y, v[i].y, acc[i]));
+        for (int i = 0; i < 16; ++i) {
+          const int k = N == R0 ? stockham_out_index<R0>(t, N, 1, i) : stockham_out_index<16>(t, N, N / 16, i);
+          float mult;
+          const int j = welch_slot(g, k, mult);
+          if (j >= 0) srow[j] = fmaf(v[i].x, v[i].x, v[i].y * v[i].y) * g.scale * mult;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = fmaf(v[i].x, v[i].x, fmaf(v[i].y, v[i].y, acc[i]));
+      }
     }
     __syncthreads();  // LDS reads of this segment done before the next one writes
   }
+  if constexpr (SEG) return;
   // bins owned by this thread: output positions of the last pass
   if (!act) return;
   float *__restrict__ row = rows + (int64_t)f * g.n_win;
@@ -630,6 +645,9 @@ __global__ __launch_bounds__(MAXT, 1) void welch_rows_kernel(const v2f *__restri
 // per segment from four powers per stage (w, w^2, w^4, w^8; at most three products deep).
 // PRUNE (W <= 2N/RL): the fftshift crop keeps only last-stage outputs 0 and RL-1, so the
 // last stage forms just those two per block.
+// SEG (median / max detectors): as welch_rows_kernel's -- every segment's kept bins to
+// rows[(f nseg + s) n_win + j] at the segment's absolute index s, so the split form needs no
+// second launch.
 // Register plans (measured on MI355X):
 #ifndef ZFFT_DIF_BUF
 #define ZFFT_DIF_BUF 1  // segment and window loads through buffer resources (0: global loads)
@@ -687,7 +705,7 @@ __device__ __forceinline__ int dif_bin(int q) {
   return k;
 }
 
-template <int N, bool PRUNE, bool HALF>
+template <int N, bool PRUNE, bool HALF, bool SEG = false>
 __global__ __launch_bounds__(Dif<N>::NT, PRUNE ? Dif<N>::WAVES_PRUNE : Dif<N>::WAVES_FULL)
 void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__restrict__ win,
                       const v2f *__restrict__ tw, WelchGeom g, float *__restrict__ rows, int frames) {
@@ -859,6 +877,8 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
 #pragma unroll
     for (int m = 0; m < 16; ++m) v[m] = img[dif_slot(16 * t + m)];
     constexpr int RL = D::RL;
+    float pw[SEG ? NACC : 1];  // SEG: this segment's |X|^2, in acc's order
+    (void)pw;
 #pragma unroll
     for (int u = 0; u < 16 / RL; ++u) {
       v2f *blkv = v + RL * u;
@@ -869,12 +889,34 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
           a0 += blkv[m];
           a1 += m == 0 ? blkv[0] : cmul2(blkv[m], w16((16 - (16 / RL) * m) & 15));
         }
-        acc[2 * u] = fmaf(a0.x, a0.x, fmaf(a0.y, a0.y, acc[2 * u]));
-        acc[2 * u + 1] = fmaf(a1.x, a1.x, fmaf(a1.y, a1.y, acc[2 * u + 1]));
+        if constexpr (SEG) {
+          pw[2 * u] = fmaf(a0.x, a0.x, a0.y * a0.y);
+          pw[2 * u + 1] = fmaf(a1.x, a1.x, a1.y * a1.y);
+        } else {
+          acc[2 * u] = fmaf(a0.x, a0.x, fmaf(a0.y, a0.y, acc[2 * u]));
+          acc[2 * u + 1] = fmaf(a1.x, a1.x, fmaf(a1.y, a1.y, acc[2 * u + 1]));
+        }
       } else {
         dft<RL>(blkv);
+        if constexpr (SEG) {
 #pragma unroll
-        for (int m = 0; m < RL; ++m) acc[RL * u + m] = fmaf(blkv[m].x, blkv[m].x, fmaf(blkv[m].y, blkv[m].y, acc[RL * u + m]));
+          for (int m = 0; m < RL; ++m) pw[RL * u + m] = fmaf(blkv[m].x, blkv[m].x, blkv[m].y * blkv[m].y);
+        } else {
+#pragma unroll
+          for (int m = 0; m < RL; ++m) acc[RL * u + m] = fmaf(blkv[m].x, blkv[m].x, fmaf(blkv[m].y, blkv[m].y, acc[RL * u + m]));
+        }
+      }
+    }
+    if constexpr (SEG) {
+      if (owner) {
+        float *__restrict__ srow = rows + ((int64_t)f * g.nseg + s) * g.n_win;
+#pragma unroll
+        for (int i = 0; i < NACC; ++i) {
+          const int q = PRUNE ? 16 * t + RL * (i >> 1) + ((i & 1) ? RL - 1 : 0) : 16 * t + i;
+          float mult;
+          const int j = welch_slot(g, dif_bin<N>(q), mult);
+          if (j >= 0) srow[j] = pw[i] * g.scale * mult;
+        }
       }
     }
     sync();  // last-stage reads done before the next segment's stage-1 stores
@@ -888,6 +930,7 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
     (void)pfb;
     for (int s = s0; s < s1; ++s) seg_step(s, pfa, pfa);
   }
+  if constexpr (SEG) return;
   const int t = threadIdx.x % T;
   if (!owner) return;
   float *__restrict__ row = g.split > 1 ? g.parts + ((int64_t)f * g.split + blockIdx.y) * g.n_win
@@ -919,15 +962,15 @@ __global__ void __launch_bounds__(256) welch_parts_kernel(const float *__restric
 #undef DIF_W
 
 constexpr int kDifMinSplit = 1024;
-template <int N>
+template <int N, bool SEG>
 static hipError_t welch_dif_launch(const float2 *x, int64_t len, const float *win, const float2 *tw,
                                    const WelchGeom &g, float *rows, int frames, hipStream_t st) {
   using D = Dif<N>;
   const size_t lds = (size_t)D::FPB * D::SLOTS * sizeof(v2f);
   const bool prune = !g.onesided && g.n_win <= 2 * N / D::RL;
   const bool half = 2 * g.step == N;
-  const void *const ks[2][2] = {{(const void *)welch_dif_kernel<N, false, false>, (const void *)welch_dif_kernel<N, false, true>},
-                                {(const void *)welch_dif_kernel<N, true, false>, (const void *)welch_dif_kernel<N, true, true>}};
+  const void *const ks[2][2] = {{(const void *)welch_dif_kernel<N, false, false, SEG>, (const void *)welch_dif_kernel<N, false, true, SEG>},
+                                {(const void *)welch_dif_kernel<N, true, false, SEG>, (const void *)welch_dif_kernel<N, true, true, SEG>}};
   static bool attr_set[2][2] = {};
   if (lds > 48 * 1024 && !attr_set[prune][half]) {
     hipError_t e = hipFuncSetAttribute(ks[prune][half], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -936,7 +979,7 @@ static hipError_t welch_dif_launch(const float2 *x, int64_t len, const float *wi
   }
   const dim3 grid((unsigned)((frames + D::FPB - 1) / D::FPB), (unsigned)g.split), block(D::NT);
 #define WELCH_DIF_GO(P, H)                                                                          \
-  hipLaunchKernelGGL((welch_dif_kernel<N, P, H>), grid, block, lds, st, (const v2f *)x, len, win, \
+  hipLaunchKernelGGL((welch_dif_kernel<N, P, H, SEG>), grid, block, lds, st, (const v2f *)x, len, win, \
                      (const v2f *)tw, g, rows, frames)
   if (prune) {
     if (half) WELCH_DIF_GO(true, true);
@@ -946,7 +989,7 @@ static hipError_t welch_dif_launch(const float2 *x, int64_t len, const float *wi
     else WELCH_DIF_GO(false, false);
   }
 #undef WELCH_DIF_GO
-  if (g.split > 1) {
+  if (g.split > 1 && !SEG) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int n = g.onesided ? g.row_len : (g.n_win & ~1);
@@ -1095,7 +1138,8 @@ __device__ __forceinline__ int welch4_k1(int t, int N1, int i) {
 // the top digit is resolved last), so that pass forms just those two sums and the thread
 // keeps 2 accumulators and 2 FFT(window) values instead of 16 (the FFT(window) gathers were
 // half the pass's time at cfg5)
-template <int R0, bool PRUNE>
+// SEG (median / max detectors): as welch_rows_kernel's, rows[(f nseg + s) n_win + j]
+template <int R0, bool PRUNE, bool SEG = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZFFT_W4_RWPE))) void welch4_rows_kernel(const v2f *__restrict__ z,
                                                           const v2f *__restrict__ tws,
                                                           const v2f *__restrict__ winf,
@@ -1163,9 +1207,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZFFT_W4_RWP
 #pragma unroll
       for (int i = 0; i < NO; ++i) v[i] -= cmul(mean, wf[i]);
     }
+    if constexpr (SEG) {
+      float *__restrict__ srow = rows + ((int64_t)f * g.nseg + s) * g.n_win;
 #pragma unroll
-    for (int i = 0; i < NO; ++i) acc[i] = fmaf(v[i].x, v[i].x, fmaf(v[i].y, v[i].y, acc[i]));
+      for (int i = 0; i < NO; ++i) {
+        float mult;
+        const int j = welch_slot(g, k2 + kN2 * welch4_k1<R0>(t, N1, out_i(i)), mult);
+        if (j >= 0) srow[j] = fmaf(v[i].x, v[i].x, v[i].y * v[i].y) * g.scale * mult;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NO; ++i) acc[i] = fmaf(v[i].x, v[i].x, fmaf(v[i].y, v[i].y, acc[i]));
+    }
   }
+  if constexpr (SEG) return;
   float *__restrict__ row = rows + (int64_t)f * g.n_win;
 #pragma unroll
   for (int i = 0; i < NO; ++i) {
@@ -1175,6 +1230,159 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZFFT_W4_RWP
     const int j = welch_slot(g, k, mult);
     if (j >= 0) row[j] = 20.f * log10f(acc[i] * g.scale * mult);
   }
+}
+
+// ------------------------------------------------------------------ Welch detector selection
+// Median / max over a frame's segments (zfft_plan_average): one thread per (frame, j) reduces
+// the nseg values seg[(f nseg + s) n_win + j] the SEG kernels above left (loads coalesced
+// across j) and writes row[j] = 20 log10(value / bias).  The values are |X|^2 >= 0, so they
+// order like their bit patterns with the sign bit cleared (a NaN above +inf: the row entry is
+// then NaN, as numpy's median and max give).  The r-th smallest key falls out of a 31-step
+// bisection on the key bits, counting keys <= the candidate per step: exact, the same for any
+// order of the values, no sorting and no per-thread array in scratch.  The keys are held
+//   REG  in NS registers (nseg <= NS <= 32: cfg2's 17, cfg3's and cfg5's 3; slots past nseg
+//        hold the key 0xffffffff, above every candidate),
+//   LDS  in the thread's own LDS entries (nseg <= kSelLdsSegs, 256 B per segment and wave:
+//        cfg1's 127 segments are 32 KB, five waves per CU) -- written and read by the same
+//        thread, no barrier,
+//   else re-read from the scratch each step (L2); max needs one pass and takes this form.
+constexpr int kSelLdsSegs = 256;  // 64 KB of LDS per wave at most
+constexpr uint32_t kSelInf = 0x7f800000u;
+__device__ __forceinline__ uint32_t sel_key(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+
+// smallest key K with count(K) = #{keys <= K} >= r (1 <= r <= nseg)
+template <class Count>
+__device__ __forceinline__ uint32_t sel_kth(int r, Count count) {
+  uint32_t ans = 0;
+  for (int b = 30; b >= 0; --b) {
+    const uint32_t cand = ans | ((1u << b) - 1u);  // the largest key with ans's prefix and bit b clear
+    if (count(cand) < r) ans |= 1u << b;
+  }
+  return ans;
+}
+
+// kmax: the largest key; count as above; above(K): the smallest key > K (one exists when called)
+template <class Count, class Above>
+__device__ __forceinline__ float sel_reduce(const WelchSelect &g, uint32_t kmax, Count count, Above above) {
+  if (kmax > kSelInf) return __uint_as_float(0x7fc00000u);
+  float val = __uint_as_float(kmax);
+  if (g.mode == 1) {  // numpy's median: the middle value, or the mean of the two middle ones
+    const int rlo = (g.nseg - 1) / 2 + 1, rhi = g.nseg / 2 + 1;
+    const uint32_t klo = sel_kth(rlo, count);
+    val = __uint_as_float(klo);
+    if (rhi != rlo && count(klo) < rhi) val = 0.5f * val + 0.5f * __uint_as_float(above(klo));
+    val *= g.inv_bias;
+  }
+  return 20.f * log10f(val);
+}
+
+template <int NS>
+__global__ __launch_bounds__(256) void welch_select_reg_kernel(const float *__restrict__ seg, WelchSelect g,
+                                                               float *__restrict__ rows) {
+  const int f = blockIdx.x / g.jblocks, j = (blockIdx.x % g.jblocks) * 256 + (int)threadIdx.x;
+  if (j >= g.row_len) return;
+  const float *__restrict__ col = seg + (int64_t)f * g.nseg * g.n_win + j;
+  uint32_t key[NS];
+  uint32_t kmax = 0;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    key[s] = 0xffffffffu;
+    if (s < g.nseg) {
+      key[s] = sel_key(col[(int64_t)s * g.n_win]);
+      kmax = max(kmax, key[s]);
+    }
+  }
+  auto count = [&](uint32_t c) {
+    int n = 0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) n += key[s] <= c ? 1 : 0;
+    return n;
+  };
+  auto above = [&](uint32_t c) {
+    uint32_t m = 0xffffffffu;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) m = key[s] > c ? min(m, key[s]) : m;
+    return m;
+  };
+  rows[(int64_t)f * g.n_win + j] = sel_reduce(g, kmax, count, above);
+}
+
+// the LDS form: the keys four segments to a 16-byte entry, entry q of lane l at [64 q + l] (a
+// wave's 64 entries contiguous: one ds_read_b128 per four keys); the last entry padded with the
+// key 0xffffffff
+__global__ __launch_bounds__(64) void welch_select_lds_kernel(const float *__restrict__ seg, WelchSelect g,
+                                                              float *__restrict__ rows) {
+  extern __shared__ uint4 sel_sh[];
+  const int lane = threadIdx.x;
+  const int f = blockIdx.x / g.jblocks, j = (blockIdx.x % g.jblocks) * 64 + lane;
+  if (j >= g.row_len) return;
+  const float *__restrict__ col = seg + (int64_t)f * g.nseg * g.n_win + j;
+  const int nq = (g.nseg + 3) >> 2;
+  uint32_t kmax = 0;
+#pragma unroll 2  // eight loads in flight per wave
+  for (int q = 0; q < nq; ++q) {
+    uint32_t k[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int s = 4 * q + i;
+      k[i] = 0xffffffffu;
+      if (s < g.nseg) {
+        k[i] = sel_key(col[(int64_t)s * g.n_win]);
+        kmax = max(kmax, k[i]);
+      }
+    }
+    sel_sh[64 * q + lane] = make_uint4(k[0], k[1], k[2], k[3]);
+  }
+  auto count = [&](uint32_t c) {
+    int n = 0;
+#pragma unroll 4
+    for (int q = 0; q < nq; ++q) {
+      const uint4 k = sel_sh[64 * q + lane];
+      n += (k.x <= c ? 1 : 0) + (k.y <= c ? 1 : 0) + (k.z <= c ? 1 : 0) + (k.w <= c ? 1 : 0);
+    }
+    return n;
+  };
+  auto above = [&](uint32_t c) {
+    uint32_t m = 0xffffffffu;
+    for (int q = 0; q < nq; ++q) {
+      const uint4 k = sel_sh[64 * q + lane];
+      m = k.x > c ? min(m, k.x) : m;
+      m = k.y > c ? min(m, k.y) : m;
+      m = k.z > c ? min(m, k.z) : m;
+      m = k.w > c ? min(m, k.w) : m;
+    }
+    return m;
+  };
+  rows[(int64_t)f * g.n_win + j] = sel_reduce(g, kmax, count, above);
+}
+
+// the keys re-read from the scratch each step
+__global__ __launch_bounds__(64) void welch_select_kernel(const float *__restrict__ seg, WelchSelect g,
+                                                          float *__restrict__ rows) {
+  const int lane = threadIdx.x;
+  const int f = blockIdx.x / g.jblocks, j = (blockIdx.x % g.jblocks) * 64 + lane;
+  if (j >= g.row_len) return;
+  const float *__restrict__ col = seg + (int64_t)f * g.nseg * g.n_win + j;
+  auto key = [&](int s) { return sel_key(col[(int64_t)s * g.n_win]); };
+  uint32_t kmax = 0;
+#pragma unroll 8  // eight loads in flight per wave (one at a time: 0.89 ms for cfg1's max)
+  for (int s = 0; s < g.nseg; ++s) kmax = max(kmax, key(s));
+  auto count = [&](uint32_t c) {
+    int n = 0;
+#pragma unroll 8
+    for (int s = 0; s < g.nseg; ++s) n += key(s) <= c ? 1 : 0;
+    return n;
+  };
+  auto above = [&](uint32_t c) {
+    uint32_t m = 0xffffffffu;
+#pragma unroll 8
+    for (int s = 0; s < g.nseg; ++s) {
+      const uint32_t k = key(s);
+      m = k > c ? min(m, k) : m;
+    }
+    return m;
+  };
+  rows[(int64_t)f * g.n_win + j] = sel_reduce(g, kmax, count, above);
 }
 
 // ------------------------------------------------------------------ waterfall ring
@@ -1433,13 +1641,13 @@ hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int fr
   return hipGetLastError();
 }
 
-template <int R0, bool PF, int MAXT>
+template <int R0, bool PF, int MAXT, bool SEG>
 static hipError_t welch_launch_t(const float2 *x, int64_t len, const float *win,
                                  const float2 *tw, const WelchGeom &g, float *rows, int frames,
                                  hipStream_t st) {
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)welch_rows_kernel<R0, PF, MAXT>,
+    hipError_t e = hipFuncSetAttribute((const void *)welch_rows_kernel<R0, PF, MAXT, SEG>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (kMaxLdsFft + kMaxLdsFft / 16 + 32) * (int)sizeof(v2f));
     if (e != hipSuccess) return e;
@@ -1447,7 +1655,7 @@ static hipError_t welch_launch_t(const float2 *x, int64_t len, const float *win,
   }
   const int T = g.n_fft / 16 > 64 ? g.n_fft / 16 : 64;
   const size_t lds = (size_t)(g.n_fft + g.n_fft / 16 + 32) * sizeof(v2f);
-  hipLaunchKernelGGL((welch_rows_kernel<R0, PF, MAXT>), dim3(frames), dim3(T), lds, st, (const v2f *)x,
+  hipLaunchKernelGGL((welch_rows_kernel<R0, PF, MAXT, SEG>), dim3(frames), dim3(T), lds, st, (const v2f *)x,
                      len, win, (const v2f *)tw, g, rows, frames);
   return hipGetLastError();
 }
@@ -1458,35 +1666,41 @@ static hipError_t welch_launch_t(const float2 *x, int64_t len, const float *win,
 #define ZFFT_DIF_MAX 16384
 #endif
 constexpr int kDifMin = 1024, kDifMax = ZFFT_DIF_MAX;
-template <int R0>
+template <int R0, bool SEG>
 static hipError_t welch_launch(const float2 *x, int64_t len, const float *win, const float2 *tw,
                                const WelchGeom &g, float *rows, int frames, hipStream_t st) {
   if (g.nperseg == g.n_fft && g.n_fft >= kDifMin && g.n_fft <= kDifMax) {
     switch (g.n_fft) {
-      case 1024: return welch_dif_launch<1024>(x, len, win, tw, g, rows, frames, st);
-      case 2048: return welch_dif_launch<2048>(x, len, win, tw, g, rows, frames, st);
-      case 4096: return welch_dif_launch<4096>(x, len, win, tw, g, rows, frames, st);
-      case 8192: return welch_dif_launch<8192>(x, len, win, tw, g, rows, frames, st);
-      case 16384: return welch_dif_launch<16384>(x, len, win, tw, g, rows, frames, st);
+      case 1024: return welch_dif_launch<1024, SEG>(x, len, win, tw, g, rows, frames, st);
+      case 2048: return welch_dif_launch<2048, SEG>(x, len, win, tw, g, rows, frames, st);
+      case 4096: return welch_dif_launch<4096, SEG>(x, len, win, tw, g, rows, frames, st);
+      case 8192: return welch_dif_launch<8192, SEG>(x, len, win, tw, g, rows, frames, st);
+      case 16384: return welch_dif_launch<16384, SEG>(x, len, win, tw, g, rows, frames, st);
       default: break;
     }
   }
   // threads = N/16 (>= 64): N <= 4096 -> <= 256 threads, room for the prefetch registers
-  if (g.n_fft <= 4096) return welch_launch_t<R0, true, 256>(x, len, win, tw, g, rows, frames, st);
-  if (g.n_fft <= 8192) return welch_launch_t<R0, false, 512>(x, len, win, tw, g, rows, frames, st);
-  return welch_launch_t<R0, false, 1024>(x, len, win, tw, g, rows, frames, st);
+  if (g.n_fft <= 4096) return welch_launch_t<R0, true, 256, SEG>(x, len, win, tw, g, rows, frames, st);
+  if (g.n_fft <= 8192) return welch_launch_t<R0, false, 512, SEG>(x, len, win, tw, g, rows, frames, st);
+  return welch_launch_t<R0, false, 1024, SEG>(x, len, win, tw, g, rows, frames, st);
 }
 
 // x: natural layout, frame f at x + f*len (the caller's frames at zoom 1, otherwise the
 // last decimation stage's output).  N = R0 * 16^p.
-hipError_t launch_welch_rows(const float2 *x, int64_t len, const float *win, const float2 *tw,
-                             const WelchGeom &g, float *rows, int frames, hipStream_t st) {
+template <bool SEG>
+static hipError_t welch_rows_by_radix(const float2 *x, int64_t len, const float *win, const float2 *tw,
+                                      const WelchGeom &g, float *rows, int frames, hipStream_t st) {
   switch (g.log2n % 4) {
-    case 0: return welch_launch<16>(x, len, win, tw, g, rows, frames, st);
-    case 1: return welch_launch<2>(x, len, win, tw, g, rows, frames, st);
-    case 2: return welch_launch<4>(x, len, win, tw, g, rows, frames, st);
-    default: return welch_launch<8>(x, len, win, tw, g, rows, frames, st);
+    case 0: return welch_launch<16, SEG>(x, len, win, tw, g, rows, frames, st);
+    case 1: return welch_launch<2, SEG>(x, len, win, tw, g, rows, frames, st);
+    case 2: return welch_launch<4, SEG>(x, len, win, tw, g, rows, frames, st);
+    default: return welch_launch<8, SEG>(x, len, win, tw, g, rows, frames, st);
   }
+}
+hipError_t launch_welch_rows(const float2 *x, int64_t len, const float *win, const float2 *tw,
+                             const WelchGeom &g, float *rows, int frames, hipStream_t st, bool segs) {
+  return segs ? welch_rows_by_radix<true>(x, len, win, tw, g, rows, frames, st)
+              : welch_rows_by_radix<false>(x, len, win, tw, g, rows, frames, st);
 }
 
 template <int CPW>
@@ -1509,7 +1723,7 @@ static hipError_t welch4_cols_launch(const void *x, int64_t len, const float *wi
 
 hipError_t launch_welch4(const float2 *x, int64_t len, const float *win, const float2 *tw,
                          const float2 *tws, const float2 *winf, const WelchGeom &g, float2 *means,
-                         float2 *z, float *rows, int frames, hipStream_t st) {
+                         float2 *z, float *rows, int frames, hipStream_t st, bool seg_out) {
   const int N1 = g.n_fft / kN2;
   if (N1 < 16 || N1 > 256 || g.n_fft != N1 * kN2) return hipErrorInvalidValue;
   if (g.fused_mean && !winf) return hipErrorInvalidValue;
@@ -1538,12 +1752,16 @@ hipError_t launch_welch4(const float2 *x, int64_t len, const float *win, const f
 #define ZFFT_W4_PRUNE 1
 #endif
   const bool prune = ZFFT_W4_PRUNE && !g.onesided && N1 > 16 && (int64_t)g.n_win * 8 <= g.n_fft;
-#define W4_ROWS(R)                                                                                    \
-  do {                                                                                                \
-    if (prune)                                                                                        \
-      hipLaunchKernelGGL((welch4_rows_kernel<R, true>), grid, block, lds, st, zc, tc, wc, mc, g, rows);  \
-    else                                                                                              \
-      hipLaunchKernelGGL((welch4_rows_kernel<R, false>), grid, block, lds, st, zc, tc, wc, mc, g, rows); \
+#define W4_ROWS(R)                                                                                                \
+  do {                                                                                                            \
+    if (seg_out && prune)                                                                                         \
+      hipLaunchKernelGGL((welch4_rows_kernel<R, true, true>), grid, block, lds, st, zc, tc, wc, mc, g, rows);     \
+    else if (seg_out)                                                                                             \
+      hipLaunchKernelGGL((welch4_rows_kernel<R, false, true>), grid, block, lds, st, zc, tc, wc, mc, g, rows);    \
+    else if (prune)                                                                                               \
+      hipLaunchKernelGGL((welch4_rows_kernel<R, true>), grid, block, lds, st, zc, tc, wc, mc, g, rows);           \
+    else                                                                                                          \
+      hipLaunchKernelGGL((welch4_rows_kernel<R, false>), grid, block, lds, st, zc, tc, wc, mc, g, rows);          \
   } while (0)
   switch (ilog2_dev(N1) % 4) {
     case 0: W4_ROWS(16); break;
@@ -1552,6 +1770,36 @@ hipError_t launch_welch4(const float2 *x, int64_t len, const float *win, const f
     default: W4_ROWS(8); break;
   }
 #undef W4_ROWS
+  return hipGetLastError();
+}
+
+hipError_t launch_welch_select(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st) {
+  if (g.nseg < 1 || g.row_len < 1 || g.row_len > g.n_win || (g.mode != 1 && g.mode != 2) || frames < 1)
+    return hipErrorInvalidValue;
+  const bool reg = g.nseg <= 32;
+  g.jblocks = (g.row_len + (reg ? 255 : 63)) / (reg ? 256 : 64);
+  if ((int64_t)frames * g.jblocks > INT32_MAX) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(frames * g.jblocks));
+  if (reg) {
+#define SEL_REG(NS) hipLaunchKernelGGL(welch_select_reg_kernel<NS>, grid, dim3(256), 0, st, seg, g, rows)
+    if (g.nseg <= 4) SEL_REG(4);
+    else if (g.nseg <= 8) SEL_REG(8);
+    else if (g.nseg <= 16) SEL_REG(16);
+    else if (g.nseg <= 24) SEL_REG(24);
+    else SEL_REG(32);
+#undef SEL_REG
+  } else if (g.mode == 1 && g.nseg <= kSelLdsSegs) {  // (max is the first pass alone: no LDS)
+    static bool attr = false;
+    if (!attr) {
+      const hipError_t e = hipFuncSetAttribute((const void *)welch_select_lds_kernel,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, kSelLdsSegs * 256);
+      if (e != hipSuccess) return e;
+      attr = true;
+    }
+    hipLaunchKernelGGL(welch_select_lds_kernel, grid, dim3(64), (size_t)((g.nseg + 3) / 4) * 1024, st, seg, g, rows);
+  } else {
+    hipLaunchKernelGGL(welch_select_kernel, grid, dim3(64), 0, st, seg, g, rows);
+  }
   return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 
 #include "cheby1_q2.h"
 #include "zfft.h"
+#include "zfft_median_bias.h"
 #include "zfft_plan.h"
 #include "zfft_schedule.h"
 
@@ -194,6 +195,14 @@ int check_lengths(const zfft_plan *p, int64_t L, int32_t frames, std::vector<int
 #define ZFFT_WELCH4_CHUNK_MB 0  // chunks of 48/96/192 MB measured 3.1x/1.8x/1.4x slower (cfg5)
 #endif
 constexpr size_t kWelch4ChunkBytes = (size_t)ZFFT_WELCH4_CHUNK_MB << 20;  // 0: one launch set
+// Segment scratch of the median / max detectors per chunk of frames.  A cap of the Infinity
+// Cache's size (256 MB, so that welch_select reads what the Welch kernels just wrote) measured
+// slower than one launch set wherever it splits a call (cfg1's 4096 frames, 532 MB: 2.95 against
+// 2.61 ms), so the cap only bounds the workspace.
+#ifndef ZFFT_AVG_SCRATCH_MB
+#define ZFFT_AVG_SCRATCH_MB 1024
+#endif
+constexpr size_t kAvgScratchBytes = (size_t)ZFFT_AVG_SCRATCH_MB << 20;
 constexpr int kMaxLoRows = 256;  // LO rows of set_lo_frames (each n_samples x 8 B)
 // zfft_process pipelining: inputs of >= 64 MB go in batches of about 1 GB (at least two).
 constexpr size_t kPipeMinBytes = (size_t)64 << 20;
@@ -245,8 +254,10 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
   w.nperseg = nperseg;
   w.step = nperseg - nperseg / 2;
   w.nseg = (int)((Ld - nperseg) / w.step + 1);
-  // density scaling 1/(fs*sum(w^2)) and the segment mean (csd average='mean')
-  w.scale = (float)(1.0 / (p->cfg.fs * p->win_ss * (double)w.nseg));
+  // density scaling 1/(fs*sum(w^2)) and the segment mean (csd average='mean'); the median and
+  // max detectors (zfft_plan_average) take the segments' densities one by one
+  const bool segs = p->average != ZFFT_AVG_MEAN;
+  w.scale = (float)(1.0 / (p->cfg.fs * p->win_ss * (segs ? 1.0 : (double)w.nseg)));
   if (onesided(p)) {
     w.onesided = 1;
     w.row_a = N / 2 - p->cfg.n_win / 2;
@@ -255,40 +266,68 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
   // auto: four-step above 16384 (the only form there); N <= 16384 runs one workgroup per
   // frame (the in-place DIF kernel from N = 1024)
   const bool four = p->welch == 2 || (p->welch == 0 && N > kWelchOneWgMax);
-  hipError_t e;
-  if (four) {
-    // frames in chunks whose intermediate Z (nseg x N complex64 per frame) stays in the
-    // 256 MB Infinity Cache between the column and the row pass instead of round-tripping
-    // through HBM
-    const size_t zf = (size_t)w.nseg * N * sizeof(float2);
-    const int chunk = kWelch4ChunkBytes > 0
-                          ? (int)std::max<size_t>(1, std::min<size_t>(frames, kWelch4ChunkBytes / zf))
-                          : frames;
-    w.fused_mean = nperseg == N ? 1 : 0;  // partial sums from the column pass (kN2-column groups)
-    e = p->means.ensure((size_t)chunk * w.nseg * std::max(1, N / 256 / 16) * sizeof(float2));
-    if (e == hipSuccess) e = p->z4.ensure((size_t)chunk * zf);
-    if (e != hipSuccess) return fail(ZFFT_ENOMEM, "four-step Welch workspace allocation failed");
+  // floats per frame a Welch launch writes: the row, or (segs) every segment's bins
+  const int64_t ostride = (int64_t)(segs ? w.nseg : 1) * p->cfg.n_win;
+  // the Welch launches of nf frames from xc: dB rows into out, or (segs) the segments' bins
+  auto welch = [&](const float2 *xc, float *out, int nf) -> int {
+    hipError_t e;
+    if (four) {
+      // frames in chunks whose intermediate Z (nseg x N complex64 per frame) stays in the
+      // 256 MB Infinity Cache between the column and the row pass instead of round-tripping
+      // through HBM
+      const size_t zf = (size_t)w.nseg * N * sizeof(float2);
+      const int chunk = kWelch4ChunkBytes > 0
+                            ? (int)std::max<size_t>(1, std::min<size_t>(nf, kWelch4ChunkBytes / zf))
+                            : nf;
+      w.fused_mean = nperseg == N ? 1 : 0;  // partial sums from the column pass (kN2-column groups)
+      e = p->means.ensure((size_t)chunk * w.nseg * std::max(1, N / 256 / 16) * sizeof(float2));
+      if (e == hipSuccess) e = p->z4.ensure((size_t)chunk * zf);
+      if (e != hipSuccess) return fail(ZFFT_ENOMEM, "four-step Welch workspace allocation failed");
+      for (int f0 = 0; f0 < nf; f0 += chunk) {
+        const int nc = std::min(chunk, nf - f0);
+        e = launch_welch4(xc + (int64_t)f0 * Ld, Ld, p->win.as<float>(), p->tw.as<float2>(),
+                          p->tws.as<float2>(), w.fused_mean ? p->winf.as<float2>() : nullptr, w,
+                          p->means.as<float2>(), p->z4.as<float2>(), out + (int64_t)f0 * ostride, nc, st,
+                          segs);
+        if (e != hipSuccess) return hip_fail(e, "welch4 launch");
+      }
+    } else {
+      // few frames per call (the reference's one): each frame's segments over several
+      // workgroups (welch_dif_split), partial PSDs summed by a second launch
+      w.split = nperseg == N ? welch_dif_split(N, w.nseg, nf) : 1;
+      p->last_split = w.split;
+      if (w.split > 1 && !segs) {
+        e = p->wparts.ensure((size_t)nf * w.split * p->cfg.n_win * sizeof(float));
+        if (e != hipSuccess) return fail(ZFFT_ENOMEM, "Welch workspace allocation failed");
+        w.parts = p->wparts.as<float>();
+      }
+      e = launch_welch_rows(xc, Ld, p->win.as<float>(), p->tw.as<float2>(), w, out, nf, st, segs);
+      if (e != hipSuccess) return hip_fail(e, "welch_rows launch");
+    }
+    return ZFFT_OK;
+  };
+  if (!segs) {
+    rc = welch(x, d_rows, frames);
+    if (rc) return rc;
+    mark(p, st, four ? "welch4" : "welch_rows");
+  } else {
+    // the frames in chunks whose segment scratch stays within the cap; at least one frame
+    const size_t per = (size_t)ostride * sizeof(float);
+    const size_t cap = p->avg_cap ? p->avg_cap : kAvgScratchBytes;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)frames, cap / per));
+    if (p->wsegs.ensure((size_t)chunk * per) != hipSuccess)
+      return fail(ZFFT_ENOMEM, "Welch segment workspace allocation failed");
+    WelchSelect sel{w.nseg, p->cfg.n_win, row_length(p), p->average,
+                    p->average == ZFFT_AVG_MEDIAN ? (float)(1.0 / median_bias(w.nseg)) : 1.f};
     for (int f0 = 0; f0 < frames; f0 += chunk) {
       const int nf = std::min(chunk, frames - f0);
-      e = launch_welch4(x + (int64_t)f0 * Ld, Ld, p->win.as<float>(), p->tw.as<float2>(),
-                        p->tws.as<float2>(), w.fused_mean ? p->winf.as<float2>() : nullptr, w,
-                        p->means.as<float2>(), p->z4.as<float2>(),
-                        d_rows + (int64_t)f0 * p->cfg.n_win, nf, st);
-      if (e != hipSuccess) return hip_fail(e, "welch4 launch");
+      rc = welch(x + (int64_t)f0 * Ld, p->wsegs.as<float>(), nf);
+      if (rc) return rc;
+      mark(p, st, four ? "welch4_segs" : "welch_segs");
+      const hipError_t e = launch_welch_select(p->wsegs.as<float>(), sel, d_rows + (int64_t)f0 * p->cfg.n_win, nf, st);
+      if (e != hipSuccess) return hip_fail(e, "welch_select launch");
+      mark(p, st, "welch_select");
     }
-    mark(p, st, "welch4");
-  } else {
-    // few frames per call (the reference's one): each frame's segments over several
-    // workgroups (welch_dif_split), partial PSDs summed by a second launch
-    if (nperseg == N) w.split = welch_dif_split(N, w.nseg, frames);
-    if (w.split > 1) {
-      e = p->wparts.ensure((size_t)frames * w.split * p->cfg.n_win * sizeof(float));
-      if (e != hipSuccess) return fail(ZFFT_ENOMEM, "Welch workspace allocation failed");
-      w.parts = p->wparts.as<float>();
-    }
-    e = launch_welch_rows(x, Ld, p->win.as<float>(), p->tw.as<float2>(), w, d_rows, frames, st);
-    if (e != hipSuccess) return hip_fail(e, "welch_rows launch");
-    mark(p, st, "welch_rows");
   }
   p->last_row = d_rows + (int64_t)(frames - 1) * p->cfg.n_win;
   return ZFFT_OK;
@@ -299,6 +338,16 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
 // Test hook (not part of include/zfft.h): how often the plan has waited on the host for its
 // enqueued work (a table upload that must not overwrite data in use, a synchronous call).
 extern "C" int64_t zfft__plan_quiesce_count(const zfft_plan *p) { return p ? p->n_quiesce : -1; }
+
+// Test hooks (not part of include/zfft.h): the cap of the median / max detectors' segment
+// scratch in bytes (0 = the default), so that a small call runs in several chunks; and the
+// number of workgroups per frame (WelchGeom::split) of the plan's last one-workgroup Welch launch.
+extern "C" int zfft__plan_average_cap(zfft_plan *p, int64_t bytes) {
+  if (!p || bytes < 0) return ZFFT_EINVAL;
+  p->avg_cap = (size_t)bytes;
+  return ZFFT_OK;
+}
+extern "C" int zfft__plan_welch_split(const zfft_plan *p) { return p ? p->last_split : -1; }
 
 // Test hook (not part of include/zfft.h; needs no device): the decimator schedule a call of
 // `frames` frames of L samples takes on a plan of this zoom, in_dtype and forced path --
@@ -489,6 +538,14 @@ int zfft_plan_welch(zfft_plan *p, int32_t mode) {
   if (mode == 2 && p->cfg.n_fft < 4096)
     return fail(ZFFT_EINVAL, "four-step Welch needs n_fft >= 4096 (N1 = n_fft/256 >= 16)");
   p->welch = mode;
+  return ZFFT_OK;
+}
+
+int zfft_plan_average(zfft_plan *p, int32_t mode) {
+  if (!p) return fail(ZFFT_EINVAL, "null plan");
+  if (mode != ZFFT_AVG_MEAN && mode != ZFFT_AVG_MEDIAN && mode != ZFFT_AVG_MAX)
+    return fail(ZFFT_EINVAL, "average must be 0 (mean), 1 (median) or 2 (max)");
+  p->average = mode;
   return ZFFT_OK;
 }
 

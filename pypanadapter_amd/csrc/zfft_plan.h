@@ -81,6 +81,13 @@ struct zfft_plan {
   DevBuf pc_tab4;  // PC zoom 4: PcTab4
   DevBuf pc_tab2;  // PC zoom 2: PcTab2
   DevBuf wparts;   // split DIF Welch: partial PSDs (frames x split x n_win floats)
+  // Welch detector (zfft_plan_average): ZFFT_AVG_MEAN sums the segments in the Welch kernels;
+  // median / max leave every segment's bins in wsegs (frames x nseg x n_win floats, the frames
+  // of a call in chunks of at most avg_cap bytes; 0 = the default cap) for welch_select
+  int average = 0;
+  size_t avg_cap = 0;   // test hook zfft__plan_average_cap
+  DevBuf wsegs;
+  int last_split = 1;   // WelchGeom::split of the last Welch launch (test hook zfft__plan_welch_split)
   DevBuf lo1;      // unit LO table (the blocked passes after the PC head mix with it)
   int64_t lo1_n = 0;  // entries of lo1 filled (a failed fill leaves it short: refilled next call)
   int64_t n_quiesce = 0;   // host waits on enqueued work (test hook zfft__plan_quiesce_count)

@@ -47,12 +47,15 @@ class ZoomFFT:
 
     def __init__(self, n_fft: int, zoom: int, fs: float, n_win: int | None = None,
                  window="hamming", f_lo: float = 1.0, scroll: int = 1, device: int = 0,
-                 in_dtype: str = "complex64", flip: bool = False):
+                 in_dtype: str = "complex64", flip: bool = False, average: str = "mean"):
         """in_dtype: "complex64" (complex ndarray), "complex32" (float16 interleaved I,Q,
         shape (..., 2L)), "cu8" (RTL-SDR uint8 interleaved I,Q, value b/127.5 - 1) or "f32"
         (real samples, AudioPan; at zoom 1 the rows are one-sided and `row_length` long).
-        flip: reverse every frame on load (the sources' np.flip, S:541-543)."""
+        flip: reverse every frame on load (the sources' np.flip, S:541-543).
+        average: the Welch detector over a frame's segments, see `set_average`."""
         self.lib = _lib.load()
+        if average not in _lib.AVERAGES:
+            raise ValueError(f"average must be one of {sorted(_lib.AVERAGES)}")
         if in_dtype not in IN_DTYPES:
             raise ValueError(f"in_dtype must be one of {sorted(IN_DTYPES)}")
         self.in_dtype, self.flip = in_dtype, bool(flip)
@@ -74,6 +77,9 @@ class ZoomFFT:
                                         ctypes.byref(self._plan)), "zfft_plan_create")
         self.scroll = int(scroll)
         self.device = int(device)
+        self.average = "mean"
+        if average != "mean":
+            self.set_average(average)
 
     # ---------------------------------------------------------------- lifetime
     def close(self):
@@ -102,7 +108,7 @@ class ZoomFFT:
     def timings(self) -> list:
         """Per-launch ms of the last process call (needs set_timing(True)), in launch order,
         one per name of `launch_names()`: XA schedule [xa_stage_mix, xa_stage, ..., welch_rows
-        | welch4]; blocked schedules a forward and a backward pass per stage; a batched host
+        | welch4 (median / max: welch_segs | welch4_segs, then welch_select)]; blocked schedules a forward and a backward pass per stage; a batched host
         call repeats the sequence per batch after a "batch_wait" interval."""
         buf = (ctypes.c_float * 1024)()
         n = ctypes.c_int32()
@@ -138,6 +144,18 @@ class ZoomFFT:
     def set_welch(self, mode: int) -> None:
         """0 auto, 1 one workgroup per frame (n_fft <= 16384), 2 four-step (n_fft >= 4096)."""
         check(self.lib.zfft_plan_welch(self._plan, int(mode)), "zfft_plan_welch")
+
+    def set_average(self, average: str) -> None:
+        """How a frame's Welch segments combine into its row (zfft_plan_average): "mean"
+        (scipy.signal.welch's default, the reference's call), "median"
+        (scipy.signal.welch(average='median'): the bias-corrected median, which an impulse in a
+        few segments does not lift) or "max" (peak hold over the frame's segments, for
+        transmissions shorter than a frame).  Holds for every later call, `IQRing.process`
+        included, until changed."""
+        if average not in _lib.AVERAGES:
+            raise ValueError(f"average must be one of {sorted(_lib.AVERAGES)}")
+        check(self.lib.zfft_plan_average(self._plan, _lib.AVERAGES[average]), "zfft_plan_average")
+        self.average = average
 
     def set_lo_frames(self, f_lo, frames_per_lo: int = 1) -> None:
         """Batched multi-IF (config 4): frame f of each call is mixed with

@@ -41,20 +41,21 @@ class PlanCache:
         self.plan: ZoomFFT | None = None
 
     def get(self, fs, n_fft, zoom, n_win, window="hamming", f_lo=1.0,
-            in_dtype="complex64") -> ZoomFFT:
-        key = (float(fs), int(n_fft), int(zoom), int(n_win), _key(window), float(f_lo), in_dtype)
+            in_dtype="complex64", average="mean") -> ZoomFFT:
+        key = (float(fs), int(n_fft), int(zoom), int(n_win), _key(window), float(f_lo), in_dtype,
+               average)
         if key != self._key:
             if self.plan is not None:
                 self.plan.close()
             self.plan = ZoomFFT(n_fft, zoom, fs, n_win=n_win, window=window, f_lo=f_lo,
-                                device=self.device, in_dtype=in_dtype)
+                                device=self.device, in_dtype=in_dtype, average=average)
             self._key = key
         return self.plan
 
 
 def _cache(device: int, purpose: str = "rows") -> PlanCache:
-    """Per thread, device and purpose: zoomfft and psd_row keep separate plans, so code
-    alternating the two does not rebuild a plan on every call."""
+    """Per thread, device and purpose: zoomfft and psd_row (each detector of it) keep separate
+    plans, so code alternating them does not rebuild a plan on every call."""
     caches = getattr(_tls, "caches", None)
     if caches is None:
         caches = _tls.caches = {}
@@ -71,29 +72,34 @@ def zoomfft(x, ratio: int, fs: float, f_lo: float = 1.0, device: int = 0) -> np.
 
 
 def psd_row(chunk, fs: float, fft_size: int, fft_ratio: int, n_win: int | None = None,
-            window="hamming", f_lo: float = 1.0, device: int = 0) -> np.ndarray:
+            window="hamming", f_lo: float = 1.0, device: int = 0,
+            average: str = "mean") -> np.ndarray:
     """The row ApplicationDisplay.update hands to waterfall.image_update (S:2102-2119).
 
     Returns a fresh, writable float64 array (the reference's dtype), length n_win
     (default N / zoom, i.e. N_WIN after fft_change, S:1757).  A real chunk (AudioPan,
     S:712-713) runs as real input: mixed to complex by the LO when zooming, and through
     welch's one-sided branch at zoom 1, whose row is the reference's shorter slice.
+    average: "mean" (the reference's welch call), "median" (welch(average='median'): impulsive
+    interference in a few segments does not lift the row) or "max" (peak hold over the chunk's
+    segments); see ZoomFFT.set_average.
     """
     n_win = int(fft_size) // int(fft_ratio) if n_win is None else int(n_win)
     real = not np.iscomplexobj(chunk)
-    plan = _cache(device).get(fs, fft_size, fft_ratio, n_win, window, f_lo,
-                              "f32" if real else "complex64")
+    purpose = "rows" if average == "mean" else "rows/" + str(average)
+    plan = _cache(device, purpose).get(fs, fft_size, fft_ratio, n_win, window, f_lo,
+                                       "f32" if real else "complex64", average)
     return plan.rows(chunk).astype(np.float64)
 
 
 def thread_psd_row(chunk, fs: float, fft_size: int, fft_ratio: int, window="hamming",
-                   f_lo: float = 1.0, device: int = 0):
+                   f_lo: float = 1.0, device: int = 0, average: str = "mean"):
     """PSD.update of the threaded variant (pypanadapter_thread.py:1513-1548): skips chunks
     shorter than fft_size (T:1522-1523) and crops W = 2*int(0.5*N/zoom) (T:1542)."""
     if len(chunk) < fft_size:
         return None
     n_win = 2 * int(0.5 * fft_size / fft_ratio)
-    return psd_row(chunk, fs, fft_size, fft_ratio, n_win, window, f_lo, device)
+    return psd_row(chunk, fs, fft_size, fft_ratio, n_win, window, f_lo, device, average)
 
 
 class Waterfall:
