@@ -304,6 +304,37 @@ int zfft_plan_welch(zfft_plan *plan, int32_t mode);
 enum zfft_average { ZFFT_AVG_MEAN = 0, ZFFT_AVG_MEDIAN = 1, ZFFT_AVG_MAX = 2 };
 int zfft_plan_average(zfft_plan *plan, int32_t mode);
 
+/* Time-resolved waterfall: segments per waterfall line.  0 (default) = the whole frame: one row
+ * per frame, exactly the kernels and bytes of a plan that never called this.  g >= 1: a frame's
+ * nseg segments, in the order Welch receives them (after flip_input), form R = ceil(nseg / g)
+ * groups of g consecutive segments (the last group holds the remaining 1..g); row r is the
+ * plan's detector over group r:
+ *   mean   20 log10( (1/n_r) sum_{s in group r} P_s[k] )
+ *   median 20 log10( median_{s in group r} P_s[k] / bias(n_r) )   (numpy's median, scipy's bias)
+ *   max    20 log10( max_{s in group r} P_s[k] )
+ * with P_s and the crop as in zfft_plan_average, n_r the group's size: g = 1 is
+ * scipy.signal.spectrogram(mode='psd') through the reference's crop and dB.  g >= nseg gives
+ * R = 1 and takes the g = 0 path.  Rows of frame f are rows_out[(f R + r) n_win ...], in time
+ * order, so zfft_process* needs n_frames * R * n_win floats; R = zfft_line_count(...).  g < 0 is
+ * ZFFT_EINVAL.  Which kernels form the lines is the plan's choice and no part of this interface
+ * (zfft_plan_timing_names tells what ran). */
+int zfft_plan_segments_per_line(zfft_plan *plan, int32_t g);
+/* No plan, no GPU (like zfft_decimated_length): rows per frame of n_samples input samples;
+ * 1 for g = 0, for the short-input branch (L_d < n_fft) and whenever g >= nseg.  -1 for
+ * n_samples < 1, n_fft < 2, a zoom that is no power of two, or g < 0. */
+int64_t zfft_line_count(int64_t n_samples, int32_t zoom, int32_t n_fft, int32_t g);
+/* Centre time of every line in seconds from the frame's first sample, at the input rate fs: the
+ * mean over the group of scipy.signal.spectrogram's t_s = (s step + nperseg/2) zoom / fs.
+ * *count = zfft_line_count(...); ZFFT_EINVAL (with *count set) when max is smaller. */
+int zfft_line_times(int64_t n_samples, int32_t zoom, int32_t n_fft, double fs, int32_t g,
+                    double *t_out, int32_t max, int32_t *count);
+/* zfft_ring_process for a plan with g >= 1 (any plan: g = 0 gives one line): up to max_lines rows
+ * of the drained frame, *produced of them (0: the frame was shorter than n_fft).  ZFFT_EINVAL
+ * before anything is taken when max_lines < zfft_line_count(ring capacity, ...).  Plain
+ * zfft_ring_process on a plan with g >= 1 is ZFFT_EINVAL, before a frame is taken. */
+int zfft_ring_process_lines(zfft_ring *ring, zfft_plan *plan, float *rows_out, int32_t max_lines,
+                            int32_t *produced);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

@@ -66,6 +66,7 @@ EXPORTS = [
     "zfft_waterfall_render_device", "zfft_waterfall_push_render", "zfft_waterfall_push_read64",
     "zfft_host_alloc", "zfft_host_free",
     "zfft_device_count", "zfft_version",
+    "zfft_plan_segments_per_line", "zfft_line_count", "zfft_line_times", "zfft_ring_process_lines",
 ]
 
 _lib = None
@@ -140,6 +141,10 @@ def load(path: str = ""):
         "zfft_ring_take": (ctypes.c_int, [P, ctypes.POINTER(P), ctypes.POINTER(I64),
                                            ctypes.POINTER(I64)]),
         "zfft_ring_process": (ctypes.c_int, [P, P, P, ctypes.POINTER(I32)]),
+        "zfft_plan_segments_per_line": (ctypes.c_int, [P, I32]),
+        "zfft_line_count": (I64, [I64, I32, I32, I32]),
+        "zfft_line_times": (ctypes.c_int, [I64, I32, I32, D, I32, P, I32, ctypes.POINTER(I32)]),
+        "zfft_ring_process_lines": (ctypes.c_int, [P, P, P, I32, ctypes.POINTER(I32)]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

@@ -319,16 +319,28 @@ struct WelchGeom {
   int split = 1;
   float *parts = nullptr;
 };
+// Fused mean lines (zfft_plan_segments_per_line; the in-place DIF kernel only), grp >= 1: the
+// frame's rows are lines = ceil(nseg / grp) lines of grp segments, rows[(f lines + r) n_win + j];
+// WelchGeom::scale is then 1 / (fs sum(w^2) grp), scale_tail the same with the last line's
+// segment count, and WelchGeom::split counts parts of whole lines, each written by its own
+// workgroup (parts unused).  A kernel argument of its own, after the others: WelchGeom and the
+// argument layout of the mean and SEG forms stay as they were.
+struct WelchLines {
+  int grp = 0, lines = 1;
+  float scale_tail = 0.f;
+};
 // DIF Welch split for a call of `frames` frames: enough workgroups for the chip (about 768 at
 // N = 4096), at least two segments each; 1 for full batches.
 int welch_dif_split(int n_fft, int nseg, int frames);
+// The same for fused mean lines: parts of whole lines, every part at least one line.
+int welch_dif_split_lines(int n_fft, int lines, int frames);
 
 // segs (median / max detectors, zfft_plan_average): instead of the dB rows, every segment's
 // scaled linear bins into rows[(f nseg + s) n_win + j] (g.scale then without 1/nseg; the split
 // form writes them at their absolute s and needs neither g.parts nor a second launch).
 hipError_t launch_welch_rows(const float2 *x, int64_t len, const float *win, const float2 *tw,
                              const WelchGeom &g, float *rows, int frames, hipStream_t st,
-                             bool segs = false);
+                             bool segs = false, const WelchLines &ln = WelchLines());
 
 // Four-step Welch for N = N1 * 256, 16 <= N1 <= 256: means (frames*nseg), z (frames*nseg*N)
 // workspaces; tws = W_256^m (256) ++ W_N1^m (N1).  seg_out: launch_welch_rows' segs.
@@ -344,6 +356,12 @@ struct WelchSelect {
   int mode;
   float inv_bias;
   int jblocks = 0;  // (set by the launch) workgroups per frame
+  // lines (zfft_plan_segments_per_line), grp >= 1: `lines` = ceil(nseg / grp) rows per frame,
+  // rows[(f lines + r) n_win + j] the detector over segments [r grp, min(nseg, (r + 1) grp)) of
+  // frame f; inv_bias_tail is inv_bias for a shorter last line.  mode 0 (mean) exists here only:
+  // inv_bias / inv_bias_tail are then 1 / (the line's segment count).
+  int grp = 0, lines = 1;
+  float inv_bias_tail = 1.f;
 };
 hipError_t launch_welch_select(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st);
 

@@ -705,10 +705,19 @@ __device__ __forceinline__ int dif_bin(int q) {
   return k;
 }
 
-template <int N, bool PRUNE, bool HALF, bool SEG = false>
+// LINES (mean detector with zfft_plan_segments_per_line, ln.grp >= 1): the sums are kept as in
+// the mean form, but after the last segment of each group of ln.grp the owner thread writes line
+// r = s / ln.grp of the frame, 20 log10(acc * scale_r * mult) to rows[(f ln.lines + r) n_win + j]
+// (scale_r = g.scale, or ln.scale_tail for a shorter last line), zeroes acc and goes on with the
+// next group; prefetch, overlap reuse and the pruned last stage are untouched.  The split form then
+// splits a frame by whole lines: part blockIdx.y takes the lines [y lpp, (y + 1) lpp), lpp =
+// ceil(ln.lines / g.split), and writes them itself (no partial sums, no second launch); the
+// launch sizes g.split so that every part holds a line.
+template <int N, bool PRUNE, bool HALF, bool SEG = false, bool LINES = false>
 __global__ __launch_bounds__(Dif<N>::NT, PRUNE ? Dif<N>::WAVES_PRUNE : Dif<N>::WAVES_FULL)
 void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__restrict__ win,
-                      const v2f *__restrict__ tw, WelchGeom g, float *__restrict__ rows, int frames) {
+                      const v2f *__restrict__ tw, WelchGeom g, float *__restrict__ rows, int frames,
+                      WelchLines ln) {
   using D = Dif<N>;
   constexpr int T = D::T, PF = PRUNE ? D::PF_PRUNE : D::PF;
   extern __shared__ v2f dyn_sh[];
@@ -786,8 +795,10 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
   v2f pfa[PFN], pfb[PFN];  // ping-pong prefetch: segment s's values arrive in one, s+1's in
                            // the other (a single array was copied into v every segment)
   // this workgroup's segments [s0, s1): all of them, or part blockIdx.y of g.split
-  const int per = (g.nseg + g.split - 1) / g.split;
+  const int lpp = LINES ? (ln.lines + g.split - 1) / g.split : 0;  // lines per part
+  const int per = LINES ? lpp * ln.grp : (g.nseg + g.split - 1) / g.split;
   const int s0 = (int)blockIdx.y * per, s1 = min(g.nseg, s0 + per);
+  int line = (int)blockIdx.y * lpp, left = LINES ? min(ln.grp, g.nseg - s0) : 0;
   load_seg(pfa, s0, threadIdx.x % T);
   post_sum(pfa, s0 & 1, s0, threadIdx.x % T);
   sync();
@@ -907,6 +918,25 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
         }
       }
     }
+    if constexpr (LINES) {
+      if (--left == 0) {  // the group's last segment: its line, then a fresh sum
+        if (owner) {
+          float *__restrict__ lrow = rows + ((int64_t)f * ln.lines + line) * g.n_win;
+          const float sc = line == ln.lines - 1 ? ln.scale_tail : g.scale;
+#pragma unroll
+          for (int i = 0; i < NACC; ++i) {
+            const int q = PRUNE ? 16 * t + RL * (i >> 1) + ((i & 1) ? RL - 1 : 0) : 16 * t + i;
+            float mult;
+            const int j = welch_slot(g, dif_bin<N>(q), mult);
+            if (j >= 0) lrow[j] = 20.f * log10f(acc[i] * sc * mult);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < NACC; ++i) acc[i] = 0.f;
+        ++line;
+        left = min(ln.grp, g.nseg - s - 1);
+      }
+    }
     if constexpr (SEG) {
       if (owner) {
         float *__restrict__ srow = rows + ((int64_t)f * g.nseg + s) * g.n_win;
@@ -930,7 +960,7 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
     (void)pfb;
     for (int s = s0; s < s1; ++s) seg_step(s, pfa, pfa);
   }
-  if constexpr (SEG) return;
+  if constexpr (SEG || LINES) return;
   const int t = threadIdx.x % T;
   if (!owner) return;
   float *__restrict__ row = g.split > 1 ? g.parts + ((int64_t)f * g.split + blockIdx.y) * g.n_win
@@ -962,15 +992,16 @@ __global__ void __launch_bounds__(256) welch_parts_kernel(const float *__restric
 #undef DIF_W
 
 constexpr int kDifMinSplit = 1024;
-template <int N, bool SEG>
+template <int N, bool SEG, bool LINES = false>
 static hipError_t welch_dif_launch(const float2 *x, int64_t len, const float *win, const float2 *tw,
-                                   const WelchGeom &g, float *rows, int frames, hipStream_t st) {
+                                   const WelchGeom &g, float *rows, int frames, hipStream_t st,
+                                   const WelchLines &ln) {
   using D = Dif<N>;
   const size_t lds = (size_t)D::FPB * D::SLOTS * sizeof(v2f);
   const bool prune = !g.onesided && g.n_win <= 2 * N / D::RL;
   const bool half = 2 * g.step == N;
-  const void *const ks[2][2] = {{(const void *)welch_dif_kernel<N, false, false, SEG>, (const void *)welch_dif_kernel<N, false, true, SEG>},
-                                {(const void *)welch_dif_kernel<N, true, false, SEG>, (const void *)welch_dif_kernel<N, true, true, SEG>}};
+  const void *const ks[2][2] = {{(const void *)welch_dif_kernel<N, false, false, SEG, LINES>, (const void *)welch_dif_kernel<N, false, true, SEG, LINES>},
+                                {(const void *)welch_dif_kernel<N, true, false, SEG, LINES>, (const void *)welch_dif_kernel<N, true, true, SEG, LINES>}};
   static bool attr_set[2][2] = {};
   if (lds > 48 * 1024 && !attr_set[prune][half]) {
     hipError_t e = hipFuncSetAttribute(ks[prune][half], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -979,8 +1010,8 @@ static hipError_t welch_dif_launch(const float2 *x, int64_t len, const float *wi
   }
   const dim3 grid((unsigned)((frames + D::FPB - 1) / D::FPB), (unsigned)g.split), block(D::NT);
 #define WELCH_DIF_GO(P, H)                                                                          \
-  hipLaunchKernelGGL((welch_dif_kernel<N, P, H, SEG>), grid, block, lds, st, (const v2f *)x, len, win, \
-                     (const v2f *)tw, g, rows, frames)
+  hipLaunchKernelGGL((welch_dif_kernel<N, P, H, SEG, LINES>), grid, block, lds, st, (const v2f *)x, len, win, \
+                     (const v2f *)tw, g, rows, frames, ln)
   if (prune) {
     if (half) WELCH_DIF_GO(true, true);
     else WELCH_DIF_GO(true, false);
@@ -989,7 +1020,7 @@ static hipError_t welch_dif_launch(const float2 *x, int64_t len, const float *wi
     else WELCH_DIF_GO(false, false);
   }
 #undef WELCH_DIF_GO
-  if (g.split > 1 && !SEG) {
+  if (g.split > 1 && !SEG && !LINES) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int n = g.onesided ? g.row_len : (g.n_win & ~1);
@@ -1008,6 +1039,17 @@ int welch_dif_split(int n_fft, int nseg, int frames) {
   const int want = std::min((target + blocks - 1) / blocks, nseg / 2);
   const int per = (nseg + want - 1) / want;
   return (nseg + per - 1) / per;  // every part non-empty
+}
+
+int welch_dif_split_lines(int n_fft, int lines, int frames) {
+  if (n_fft < kDifMinSplit || n_fft > 16384 || lines < 2) return 1;
+  const int fpb = n_fft / 16 >= 256 ? 1 : 256 / (n_fft / 16);
+  const int blocks = (frames + fpb - 1) / fpb;
+  const int target = 768 * 256 / std::max(256, n_fft / 16);  // workgroups that fill the chip
+  if (blocks >= target / 2) return 1;
+  const int want = std::min((target + blocks - 1) / blocks, lines);
+  const int lpp = (lines + want - 1) / want;
+  return (lines + lpp - 1) / lpp;  // every part holds at least one line
 }
 
 // ------------------------------------------------------------------ Welch row, four-step
@@ -1262,10 +1304,19 @@ __device__ __forceinline__ uint32_t sel_kth(int r, Count count) {
 }
 
 // kmax: the largest key; count as above; above(K): the smallest key > K (one exists when called)
-template <class Count, class Above>
-__device__ __forceinline__ float sel_reduce(const WelchSelect &g, uint32_t kmax, Count count, Above above) {
+// LINES: a line of one or two segments (g = 1 is the spectrogram) needs no selection -- the key
+// itself, or the mean of the two (kmin: the smallest key; the general path's arithmetic)
+template <bool LINES = false, class Count, class Above>
+__device__ __forceinline__ float sel_reduce(const WelchSelect &g, uint32_t kmax, uint32_t kmin, Count count,
+                                            Above above) {
   if (kmax > kSelInf) return __uint_as_float(0x7fc00000u);
   float val = __uint_as_float(kmax);
+  if constexpr (LINES) {
+    if (g.mode == 1 && g.nseg <= 2) {
+      if (g.nseg == 2) val = 0.5f * __uint_as_float(kmin) + 0.5f * val;
+      return 20.f * log10f(val * g.inv_bias);
+    }
+  }
   if (g.mode == 1) {  // numpy's median: the middle value, or the mean of the two middle ones
     const int rlo = (g.nseg - 1) / 2 + 1, rhi = g.nseg / 2 + 1;
     const uint32_t klo = sel_kth(rlo, count);
@@ -1276,14 +1327,32 @@ __device__ __forceinline__ float sel_reduce(const WelchSelect &g, uint32_t kmax,
   return 20.f * log10f(val);
 }
 
-template <int NS>
+// The column of (virtual) frame v at j.  LINES (zfft_plan_segments_per_line): v = f lines + r is
+// line r of frame f, the segments [r grp, min(nseg, (r + 1) grp)) of that frame -- g.nseg becomes
+// the line's key count and g.inv_bias the value for that count (both uniform over the workgroup),
+// so the reductions below run on a line as they do on a frame.
+template <bool LINES>
+__device__ __forceinline__ const float *sel_col(WelchSelect &g, const float *__restrict__ seg, int v, int j) {
+  if constexpr (!LINES) {
+    return seg + (int64_t)v * g.nseg * g.n_win + j;
+  } else {
+    const int f = v / g.lines, r = v - f * g.lines;
+    const float *col = seg + ((int64_t)f * g.nseg + (int64_t)r * g.grp) * g.n_win + j;
+    const int n = min(g.grp, g.nseg - r * g.grp);
+    if (n < g.grp) g.inv_bias = g.inv_bias_tail;
+    g.nseg = n;
+    return col;
+  }
+}
+
+template <int NS, bool LINES = false>
 __global__ __launch_bounds__(256) void welch_select_reg_kernel(const float *__restrict__ seg, WelchSelect g,
                                                                float *__restrict__ rows) {
   const int f = blockIdx.x / g.jblocks, j = (blockIdx.x % g.jblocks) * 256 + (int)threadIdx.x;
   if (j >= g.row_len) return;
-  const float *__restrict__ col = seg + (int64_t)f * g.nseg * g.n_win + j;
+  const float *__restrict__ col = sel_col<LINES>(g, seg, f, j);
   uint32_t key[NS];
-  uint32_t kmax = 0;
+  uint32_t kmax = 0, kmin = 0xffffffffu;
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     key[s] = 0xffffffffu;
@@ -1291,6 +1360,7 @@ __global__ __launch_bounds__(256) void welch_select_reg_kernel(const float *__re
       key[s] = sel_key(col[(int64_t)s * g.n_win]);
       kmax = max(kmax, key[s]);
     }
+    if constexpr (LINES) kmin = min(kmin, key[s]);  // (the padding key is the largest)
   }
   auto count = [&](uint32_t c) {
     int n = 0;
@@ -1304,21 +1374,22 @@ __global__ __launch_bounds__(256) void welch_select_reg_kernel(const float *__re
     for (int s = 0; s < NS; ++s) m = key[s] > c ? min(m, key[s]) : m;
     return m;
   };
-  rows[(int64_t)f * g.n_win + j] = sel_reduce(g, kmax, count, above);
+  rows[(int64_t)f * g.n_win + j] = sel_reduce<LINES>(g, kmax, kmin, count, above);
 }
 
 // the LDS form: the keys four segments to a 16-byte entry, entry q of lane l at [64 q + l] (a
 // wave's 64 entries contiguous: one ds_read_b128 per four keys); the last entry padded with the
 // key 0xffffffff
+template <bool LINES = false>
 __global__ __launch_bounds__(64) void welch_select_lds_kernel(const float *__restrict__ seg, WelchSelect g,
                                                               float *__restrict__ rows) {
   extern __shared__ uint4 sel_sh[];
   const int lane = threadIdx.x;
   const int f = blockIdx.x / g.jblocks, j = (blockIdx.x % g.jblocks) * 64 + lane;
   if (j >= g.row_len) return;
-  const float *__restrict__ col = seg + (int64_t)f * g.nseg * g.n_win + j;
+  const float *__restrict__ col = sel_col<LINES>(g, seg, f, j);
   const int nq = (g.nseg + 3) >> 2;
-  uint32_t kmax = 0;
+  uint32_t kmax = 0, kmin = 0xffffffffu;
 #pragma unroll 2  // eight loads in flight per wave
   for (int q = 0; q < nq; ++q) {
     uint32_t k[4];
@@ -1330,6 +1401,7 @@ __global__ __launch_bounds__(64) void welch_select_lds_kernel(const float *__res
         k[i] = sel_key(col[(int64_t)s * g.n_win]);
         kmax = max(kmax, k[i]);
       }
+      if constexpr (LINES) kmin = min(kmin, k[i]);
     }
     sel_sh[64 * q + lane] = make_uint4(k[0], k[1], k[2], k[3]);
   }
@@ -1353,20 +1425,25 @@ __global__ __launch_bounds__(64) void welch_select_lds_kernel(const float *__res
     }
     return m;
   };
-  rows[(int64_t)f * g.n_win + j] = sel_reduce(g, kmax, count, above);
+  rows[(int64_t)f * g.n_win + j] = sel_reduce<LINES>(g, kmax, kmin, count, above);
 }
 
 // the keys re-read from the scratch each step
+template <bool LINES = false>
 __global__ __launch_bounds__(64) void welch_select_kernel(const float *__restrict__ seg, WelchSelect g,
                                                           float *__restrict__ rows) {
   const int lane = threadIdx.x;
   const int f = blockIdx.x / g.jblocks, j = (blockIdx.x % g.jblocks) * 64 + lane;
   if (j >= g.row_len) return;
-  const float *__restrict__ col = seg + (int64_t)f * g.nseg * g.n_win + j;
+  const float *__restrict__ col = sel_col<LINES>(g, seg, f, j);
   auto key = [&](int s) { return sel_key(col[(int64_t)s * g.n_win]); };
-  uint32_t kmax = 0;
+  uint32_t kmax = 0, kmin = 0xffffffffu;
 #pragma unroll 8  // eight loads in flight per wave (one at a time: 0.89 ms for cfg1's max)
-  for (int s = 0; s < g.nseg; ++s) kmax = max(kmax, key(s));
+  for (int s = 0; s < g.nseg; ++s) {
+    const uint32_t k = key(s);
+    kmax = max(kmax, k);
+    if constexpr (LINES) kmin = min(kmin, k);
+  }
   auto count = [&](uint32_t c) {
     int n = 0;
 #pragma unroll 8
@@ -1382,7 +1459,21 @@ __global__ __launch_bounds__(64) void welch_select_kernel(const float *__restric
     }
     return m;
   };
-  rows[(int64_t)f * g.n_win + j] = sel_reduce(g, kmax, count, above);
+  rows[(int64_t)f * g.n_win + j] = sel_reduce<LINES>(g, kmax, kmin, count, above);
+}
+
+// Mean lines (zfft_plan_segments_per_line with the mean detector): line r of frame f is
+// 20 log10 of the mean of its segments' densities, summed in segment order; one thread per
+// (line, j), g.inv_bias = 1 / (the line's segment count).
+__global__ __launch_bounds__(256) void welch_lines_mean_kernel(const float *__restrict__ seg, WelchSelect g,
+                                                               float *__restrict__ rows) {
+  const int v = blockIdx.x / g.jblocks, j = (blockIdx.x % g.jblocks) * 256 + (int)threadIdx.x;
+  if (j >= g.row_len) return;
+  const float *__restrict__ col = sel_col<true>(g, seg, v, j);
+  float sum = 0.f;
+#pragma unroll 8
+  for (int s = 0; s < g.nseg; ++s) sum += col[(int64_t)s * g.n_win];
+  rows[(int64_t)v * g.n_win + j] = 20.f * log10f(sum * g.inv_bias);
 }
 
 // ------------------------------------------------------------------ waterfall ring
@@ -1666,20 +1757,22 @@ static hipError_t welch_launch_t(const float2 *x, int64_t len, const float *win,
 #define ZFFT_DIF_MAX 16384
 #endif
 constexpr int kDifMin = 1024, kDifMax = ZFFT_DIF_MAX;
-template <int R0, bool SEG>
+template <int R0, bool SEG, bool LINES>
 static hipError_t welch_launch(const float2 *x, int64_t len, const float *win, const float2 *tw,
-                               const WelchGeom &g, float *rows, int frames, hipStream_t st) {
+                               const WelchGeom &g, float *rows, int frames, hipStream_t st,
+                               const WelchLines &ln) {
   if (g.nperseg == g.n_fft && g.n_fft >= kDifMin && g.n_fft <= kDifMax) {
     switch (g.n_fft) {
-      case 1024: return welch_dif_launch<1024, SEG>(x, len, win, tw, g, rows, frames, st);
-      case 2048: return welch_dif_launch<2048, SEG>(x, len, win, tw, g, rows, frames, st);
-      case 4096: return welch_dif_launch<4096, SEG>(x, len, win, tw, g, rows, frames, st);
-      case 8192: return welch_dif_launch<8192, SEG>(x, len, win, tw, g, rows, frames, st);
-      case 16384: return welch_dif_launch<16384, SEG>(x, len, win, tw, g, rows, frames, st);
+      case 1024: return welch_dif_launch<1024, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
+      case 2048: return welch_dif_launch<2048, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
+      case 4096: return welch_dif_launch<4096, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
+      case 8192: return welch_dif_launch<8192, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
+      case 16384: return welch_dif_launch<16384, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
       default: break;
     }
   }
   // threads = N/16 (>= 64): N <= 4096 -> <= 256 threads, room for the prefetch registers
+  if constexpr (LINES) return hipErrorInvalidValue;  // fused lines: the DIF kernel only
   if (g.n_fft <= 4096) return welch_launch_t<R0, true, 256, SEG>(x, len, win, tw, g, rows, frames, st);
   if (g.n_fft <= 8192) return welch_launch_t<R0, false, 512, SEG>(x, len, win, tw, g, rows, frames, st);
   return welch_launch_t<R0, false, 1024, SEG>(x, len, win, tw, g, rows, frames, st);
@@ -1687,18 +1780,29 @@ static hipError_t welch_launch(const float2 *x, int64_t len, const float *win, c
 
 // x: natural layout, frame f at x + f*len (the caller's frames at zoom 1, otherwise the
 // last decimation stage's output).  N = R0 * 16^p.
-template <bool SEG>
+template <bool SEG, bool LINES = false>
 static hipError_t welch_rows_by_radix(const float2 *x, int64_t len, const float *win, const float2 *tw,
-                                      const WelchGeom &g, float *rows, int frames, hipStream_t st) {
+                                      const WelchGeom &g, float *rows, int frames, hipStream_t st,
+                                      const WelchLines &ln = WelchLines()) {
   switch (g.log2n % 4) {
-    case 0: return welch_launch<16, SEG>(x, len, win, tw, g, rows, frames, st);
-    case 1: return welch_launch<2, SEG>(x, len, win, tw, g, rows, frames, st);
-    case 2: return welch_launch<4, SEG>(x, len, win, tw, g, rows, frames, st);
-    default: return welch_launch<8, SEG>(x, len, win, tw, g, rows, frames, st);
+    case 0: return welch_launch<16, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
+    case 1: return welch_launch<2, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
+    case 2: return welch_launch<4, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
+    default: return welch_launch<8, SEG, LINES>(x, len, win, tw, g, rows, frames, st, ln);
   }
 }
 hipError_t launch_welch_rows(const float2 *x, int64_t len, const float *win, const float2 *tw,
-                             const WelchGeom &g, float *rows, int frames, hipStream_t st, bool segs) {
+                             const WelchGeom &g, float *rows, int frames, hipStream_t st, bool segs,
+                             const WelchLines &ln) {
+  if (ln.grp > 0) {  // fused mean lines: 1 <= grp < nseg, full segments, never with segs
+    if (segs || ln.grp >= g.nseg || ln.lines != (g.nseg + ln.grp - 1) / ln.grp || g.nperseg != g.n_fft ||
+        g.split < 1 || g.split > ln.lines)
+      return hipErrorInvalidValue;
+    const bool dif = g.n_fft >= kDifMin && g.n_fft <= kDifMax;
+    const int lpp = (ln.lines + g.split - 1) / g.split;  // (an empty part would read past its frame)
+    if (!dif || (g.split - 1) * lpp >= ln.lines) return hipErrorInvalidValue;
+    return welch_rows_by_radix<false, true>(x, len, win, tw, g, rows, frames, st, ln);
+  }
   return segs ? welch_rows_by_radix<true>(x, len, win, tw, g, rows, frames, st)
               : welch_rows_by_radix<false>(x, len, win, tw, g, rows, frames, st);
 }
@@ -1773,33 +1877,52 @@ hipError_t launch_welch4(const float2 *x, int64_t len, const float *win, const f
   return hipGetLastError();
 }
 
-hipError_t launch_welch_select(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st) {
-  if (g.nseg < 1 || g.row_len < 1 || g.row_len > g.n_win || (g.mode != 1 && g.mode != 2) || frames < 1)
-    return hipErrorInvalidValue;
-  const bool reg = g.nseg <= 32;
+template <bool LINES>
+static hipError_t welch_select_go(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st) {
+  // keys per column: the frame's segments, or (LINES) those of a full line; vf: columns of j
+  const int keys = LINES ? g.grp : g.nseg;
+  const int64_t vf = (int64_t)frames * (LINES ? g.lines : 1);
+  const bool reg = keys <= 32;
   g.jblocks = (g.row_len + (reg ? 255 : 63)) / (reg ? 256 : 64);
-  if ((int64_t)frames * g.jblocks > INT32_MAX) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)(frames * g.jblocks));
+  if (vf * g.jblocks > INT32_MAX) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(vf * g.jblocks));
   if (reg) {
-#define SEL_REG(NS) hipLaunchKernelGGL(welch_select_reg_kernel<NS>, grid, dim3(256), 0, st, seg, g, rows)
-    if (g.nseg <= 4) SEL_REG(4);
-    else if (g.nseg <= 8) SEL_REG(8);
-    else if (g.nseg <= 16) SEL_REG(16);
-    else if (g.nseg <= 24) SEL_REG(24);
+#define SEL_REG(NS) hipLaunchKernelGGL((welch_select_reg_kernel<NS, LINES>), grid, dim3(256), 0, st, seg, g, rows)
+    if (keys <= 4) SEL_REG(4);
+    else if (keys <= 8) SEL_REG(8);
+    else if (keys <= 16) SEL_REG(16);
+    else if (keys <= 24) SEL_REG(24);
     else SEL_REG(32);
 #undef SEL_REG
-  } else if (g.mode == 1 && g.nseg <= kSelLdsSegs) {  // (max is the first pass alone: no LDS)
+  } else if (g.mode == 1 && keys <= kSelLdsSegs) {  // (max is the first pass alone: no LDS)
     static bool attr = false;
     if (!attr) {
-      const hipError_t e = hipFuncSetAttribute((const void *)welch_select_lds_kernel,
+      const hipError_t e = hipFuncSetAttribute((const void *)welch_select_lds_kernel<LINES>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, kSelLdsSegs * 256);
       if (e != hipSuccess) return e;
       attr = true;
     }
-    hipLaunchKernelGGL(welch_select_lds_kernel, grid, dim3(64), (size_t)((g.nseg + 3) / 4) * 1024, st, seg, g, rows);
+    hipLaunchKernelGGL(welch_select_lds_kernel<LINES>, grid, dim3(64), (size_t)((keys + 3) / 4) * 1024, st, seg, g, rows);
   } else {
-    hipLaunchKernelGGL(welch_select_kernel, grid, dim3(64), 0, st, seg, g, rows);
+    hipLaunchKernelGGL(welch_select_kernel<LINES>, grid, dim3(64), 0, st, seg, g, rows);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_welch_select(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st) {
+  if (g.nseg < 1 || g.row_len < 1 || g.row_len > g.n_win || frames < 1) return hipErrorInvalidValue;
+  if (g.grp == 0) {
+    if (g.mode != 1 && g.mode != 2) return hipErrorInvalidValue;
+    return welch_select_go<false>(seg, g, rows, frames, st);
+  }
+  // lines: 1 <= grp < nseg, lines = ceil(nseg / grp); mode 0 (mean) has its own kernel
+  if (g.grp < 1 || g.grp >= g.nseg || g.lines != (g.nseg + g.grp - 1) / g.grp || g.mode < 0 || g.mode > 2)
+    return hipErrorInvalidValue;
+  if (g.mode != 0) return welch_select_go<true>(seg, g, rows, frames, st);
+  g.jblocks = (g.row_len + 255) / 256;
+  const int64_t blocks = (int64_t)frames * g.lines * g.jblocks;
+  if (blocks > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(welch_lines_mean_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seg, g, rows);
   return hipGetLastError();
 }
 

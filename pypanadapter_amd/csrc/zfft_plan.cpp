@@ -99,6 +99,11 @@ int row_length(const zfft_plan *p) {
   return std::max(0, b - a);
 }
 
+int64_t lines_per_frame(const zfft_plan *p, int64_t L) {
+  const int64_t r = zfft_line_count(L, p->cfg.zoom, p->cfg.n_fft, p->seg_per_line);
+  return r < 1 ? 1 : r;  // (bad lengths are refused by the call itself)
+}
+
 }  // namespace zfft
 
 using namespace zfft;
@@ -256,18 +261,35 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
   w.nseg = (int)((Ld - nperseg) / w.step + 1);
   // density scaling 1/(fs*sum(w^2)) and the segment mean (csd average='mean'); the median and
   // max detectors (zfft_plan_average) take the segments' densities one by one
-  const bool segs = p->average != ZFFT_AVG_MEAN;
-  w.scale = (float)(1.0 / (p->cfg.fs * p->win_ss * (segs ? 1.0 : (double)w.nseg)));
+  // lines (zfft_plan_segments_per_line, 1 <= g < nseg): R rows per frame, every detector (mean
+  // too) reduced per group of g segments from the segment scratch
+  const int G = p->seg_per_line >= 1 && p->seg_per_line < w.nseg ? p->seg_per_line : 0;
+  const int R = G ? (w.nseg + G - 1) / G : 1;
+  // auto: four-step above 16384 (the only form there); N <= 16384 runs one workgroup per
+  // frame (the in-place DIF kernel from N = 1024)
+  const bool four = p->welch == 2 || (p->welch == 0 && N > kWelchOneWgMax);
+  // mean lines from the in-place DIF kernel are fused (its LINES variant writes each line from
+  // the segment loop: faster than the scratch route at every g measured);
+  // median, max, N < 1024 (the fused Stockham form measured slower) and the four-step form
+  // reduce the segment scratch
+  const bool fused = G > 0 && p->average == ZFFT_AVG_MEAN && !four && N >= 1024 && N <= kMaxLdsFft &&
+                     p->lines_route != 1;
+  const bool segs = (p->average != ZFFT_AVG_MEAN || G > 0) && !fused;
+  WelchLines ln;
+  if (fused) {
+    ln.grp = G;
+    ln.lines = R;
+    ln.scale_tail = (float)(1.0 / (p->cfg.fs * p->win_ss * (double)(w.nseg - (R - 1) * G)));
+  }
+  w.scale = (float)(1.0 / (p->cfg.fs * p->win_ss * (segs ? 1.0 : fused ? (double)G : (double)w.nseg)));
   if (onesided(p)) {
     w.onesided = 1;
     w.row_a = N / 2 - p->cfg.n_win / 2;
     w.row_len = row_length(p);
   }
-  // auto: four-step above 16384 (the only form there); N <= 16384 runs one workgroup per
-  // frame (the in-place DIF kernel from N = 1024)
-  const bool four = p->welch == 2 || (p->welch == 0 && N > kWelchOneWgMax);
-  // floats per frame a Welch launch writes: the row, or (segs) every segment's bins
-  const int64_t ostride = (int64_t)(segs ? w.nseg : 1) * p->cfg.n_win;
+  // floats per frame a Welch launch writes: the row (fused lines: R rows), or (segs) every
+  // segment's bins
+  const int64_t ostride = (int64_t)(segs ? w.nseg : R) * p->cfg.n_win;
   // the Welch launches of nf frames from xc: dB rows into out, or (segs) the segments' bins
   auto welch = [&](const float2 *xc, float *out, int nf) -> int {
     hipError_t e;
@@ -294,14 +316,14 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
     } else {
       // few frames per call (the reference's one): each frame's segments over several
       // workgroups (welch_dif_split), partial PSDs summed by a second launch
-      w.split = nperseg == N ? welch_dif_split(N, w.nseg, nf) : 1;
+      w.split = nperseg != N ? 1 : fused ? welch_dif_split_lines(N, R, nf) : welch_dif_split(N, w.nseg, nf);
       p->last_split = w.split;
-      if (w.split > 1 && !segs) {
+      if (w.split > 1 && !segs && !fused) {
         e = p->wparts.ensure((size_t)nf * w.split * p->cfg.n_win * sizeof(float));
         if (e != hipSuccess) return fail(ZFFT_ENOMEM, "Welch workspace allocation failed");
         w.parts = p->wparts.as<float>();
       }
-      e = launch_welch_rows(xc, Ld, p->win.as<float>(), p->tw.as<float2>(), w, out, nf, st, segs);
+      e = launch_welch_rows(xc, Ld, p->win.as<float>(), p->tw.as<float2>(), w, out, nf, st, segs, ln);
       if (e != hipSuccess) return hip_fail(e, "welch_rows launch");
     }
     return ZFFT_OK;
@@ -309,7 +331,7 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
   if (!segs) {
     rc = welch(x, d_rows, frames);
     if (rc) return rc;
-    mark(p, st, four ? "welch4" : "welch_rows");
+    mark(p, st, fused ? "welch_lines" : four ? "welch4" : "welch_rows");
   } else {
     // the frames in chunks whose segment scratch stays within the cap; at least one frame
     const size_t per = (size_t)ostride * sizeof(float);
@@ -319,17 +341,28 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
       return fail(ZFFT_ENOMEM, "Welch segment workspace allocation failed");
     WelchSelect sel{w.nseg, p->cfg.n_win, row_length(p), p->average,
                     p->average == ZFFT_AVG_MEDIAN ? (float)(1.0 / median_bias(w.nseg)) : 1.f};
+    if (G) {  // per line: its own segment count n_r (G, or the tail's) in the bias and the mean
+      const int tail = w.nseg - (R - 1) * G;
+      auto inv = [&](int n) {
+        return p->average == ZFFT_AVG_MEDIAN ? (float)(1.0 / median_bias(n))
+               : p->average == ZFFT_AVG_MEAN ? (float)(1.0 / (double)n) : 1.f;
+      };
+      sel.grp = G;
+      sel.lines = R;
+      sel.inv_bias = inv(G);
+      sel.inv_bias_tail = inv(tail);
+    }
     for (int f0 = 0; f0 < frames; f0 += chunk) {
       const int nf = std::min(chunk, frames - f0);
       rc = welch(x + (int64_t)f0 * Ld, p->wsegs.as<float>(), nf);
       if (rc) return rc;
       mark(p, st, four ? "welch4_segs" : "welch_segs");
-      const hipError_t e = launch_welch_select(p->wsegs.as<float>(), sel, d_rows + (int64_t)f0 * p->cfg.n_win, nf, st);
+      const hipError_t e = launch_welch_select(p->wsegs.as<float>(), sel, d_rows + (int64_t)f0 * R * p->cfg.n_win, nf, st);
       if (e != hipSuccess) return hip_fail(e, "welch_select launch");
-      mark(p, st, "welch_select");
+      mark(p, st, G && p->average == ZFFT_AVG_MEAN ? "welch_lines" : "welch_select");
     }
   }
-  p->last_row = d_rows + (int64_t)(frames - 1) * p->cfg.n_win;
+  p->last_row = d_rows + ((int64_t)frames * R - 1) * p->cfg.n_win;
   return ZFFT_OK;
 }
 
@@ -345,6 +378,13 @@ extern "C" int64_t zfft__plan_quiesce_count(const zfft_plan *p) { return p ? p->
 extern "C" int zfft__plan_average_cap(zfft_plan *p, int64_t bytes) {
   if (!p || bytes < 0) return ZFFT_EINVAL;
   p->avg_cap = (size_t)bytes;
+  return ZFFT_OK;
+}
+// Test / measurement hook: how mean lines run -- 0 the plan's choice (fused where a fused form
+// exists), 1 the segment scratch route everywhere.
+extern "C" int zfft__plan_lines_route(zfft_plan *p, int route) {
+  if (!p || route < 0 || route > 1) return ZFFT_EINVAL;
+  p->lines_route = route;
   return ZFFT_OK;
 }
 extern "C" int zfft__plan_welch_split(const zfft_plan *p) { return p ? p->last_split : -1; }
@@ -541,6 +581,46 @@ int zfft_plan_welch(zfft_plan *p, int32_t mode) {
   return ZFFT_OK;
 }
 
+int zfft_plan_segments_per_line(zfft_plan *p, int32_t g) {
+  if (!p) return fail(ZFFT_EINVAL, "null plan");
+  if (g < 0) return fail(ZFFT_EINVAL, "segments_per_line must be 0 (the whole frame) or >= 1");
+  p->seg_per_line = g;
+  return ZFFT_OK;
+}
+
+int64_t zfft_line_count(int64_t n_samples, int32_t zoom, int32_t n_fft, int32_t g) {
+  if (n_samples < 1 || n_fft < 2 || g < 0) return -1;
+  const int64_t Ld = zfft_decimated_length(n_samples, zoom);
+  if (Ld < 1) return -1;
+  if (g == 0 || Ld < n_fft) return 1;  // (short input: one segment of L_d samples)
+  const int64_t nseg = (Ld - n_fft) / (n_fft - n_fft / 2) + 1;
+  return g >= nseg ? 1 : (nseg + g - 1) / g;
+}
+
+int zfft_line_times(int64_t n_samples, int32_t zoom, int32_t n_fft, double fs, int32_t g, double *t_out,
+                    int32_t max, int32_t *count) {
+  if (!t_out || !count) return fail(ZFFT_EINVAL, "line_times: null output");
+  *count = 0;
+  const int64_t R = zfft_line_count(n_samples, zoom, n_fft, g);
+  if (R < 1 || !(fs > 0) || !std::isfinite(fs))
+    return fail(ZFFT_EINVAL, "line_times: n_samples >= 1, zoom a power of two, n_fft >= 2, fs > 0, "
+                             "segments_per_line >= 0");
+  if (R > INT32_MAX) return fail(ZFFT_EINVAL, "line_times: too many lines");
+  *count = (int32_t)R;
+  if (max < R) return fail(ZFFT_EINVAL, "line_times: max is smaller than zfft_line_count");
+  const int64_t Ld = zfft_decimated_length(n_samples, zoom);
+  const int64_t nper = Ld < n_fft ? Ld : n_fft, step = nper - nper / 2;
+  const int64_t nseg = (Ld - nper) / step + 1;
+  const int64_t G = R == 1 ? nseg : g;
+  for (int64_t r = 0; r < R; ++r) {
+    // the mean of t_s over s = r G .. r G + n - 1: its middle segment (a half step when n is even)
+    const int64_t s0 = r * G, n = std::min(G, nseg - s0);
+    const double mid = (double)s0 + 0.5 * (double)(n - 1);
+    t_out[r] = (mid * (double)step + 0.5 * (double)nper) * (double)zoom / fs;
+  }
+  return ZFFT_OK;
+}
+
 int zfft_plan_average(zfft_plan *p, int32_t mode) {
   if (!p) return fail(ZFFT_EINVAL, "null plan");
   if (mode != ZFFT_AVG_MEAN && mode != ZFFT_AVG_MEDIAN && mode != ZFFT_AVG_MAX)
@@ -599,7 +679,9 @@ int zfft_process(zfft_plan *p, const void *iq, int64_t L, int32_t frames, float 
   if (!iq || !rows_out) return fail(ZFFT_EINVAL, "null host pointer");
   if (L < 1 || frames < 1) return fail(ZFFT_EINVAL, "n_samples and n_frames must be >= 1");
   const size_t frame_bytes = (size_t)L * in_elem_bytes(p->cfg.in_dtype);
-  const size_t row_bytes = (size_t)frames * p->cfg.n_win * sizeof(float);
+  // rows per frame (zfft_plan_segments_per_line): every row-sized quantity below scales by it
+  const int64_t R = lines_per_frame(p, L);
+  const size_t row_bytes = (size_t)frames * (size_t)R * p->cfg.n_win * sizeof(float);
   // Batches: one for a small call; otherwise >= 2 so that the H2D copy of batch k+1 (copy
   // stream) runs while batch k is computed (plan stream).  From pinned memory both are
   // asynchronous; from pageable memory HIP stages the copy on this thread, which then copies
@@ -644,7 +726,7 @@ int zfft_process(zfft_plan *p, const void *iq, int64_t L, int32_t frames, float 
     if (e != hipSuccess) return hip_fail(e, "H2D copy");
     if (k > 0) mark(p, p->stream, "batch_wait");
     p->lo_first = f0;  // batch frame 0 is call frame f0 (its LO row, config 4)
-    rc = process_device(p, dst, L, nk, p->rows.as<float>() + (int64_t)f0 * p->cfg.n_win, p->stream);
+    rc = process_device(p, dst, L, nk, p->rows.as<float>() + (int64_t)f0 * R * p->cfg.n_win, p->stream);
     p->lo_first = 0;
     if (rc) return rc;
     if (nb > 1 && (e = hipEventRecord(p->comp_ev[buf], p->stream)) != hipSuccess)

@@ -87,6 +87,10 @@ struct zfft_plan {
   int average = 0;
   size_t avg_cap = 0;   // test hook zfft__plan_average_cap
   DevBuf wsegs;
+  // zfft_plan_segments_per_line: 0 = one row per frame; g >= 1: ceil(nseg / g) rows per frame,
+  // each the detector over g consecutive segments (fused mean kernels, or reduced from wsegs)
+  int seg_per_line = 0;
+  int lines_route = 0;  // hook zfft__plan_lines_route: 1 = mean lines through the scratch too
   int last_split = 1;   // WelchGeom::split of the last Welch launch (test hook zfft__plan_welch_split)
   DevBuf lo1;      // unit LO table (the blocked passes after the PC head mix with it)
   int64_t lo1_n = 0;  // entries of lo1 filled (a failed fill leaves it short: refilled next call)
@@ -138,6 +142,8 @@ int done_on(zfft_plan *p, hipStream_t st);
 int quiesce(zfft_plan *p);
 int enter(zfft_plan *p);  // null check + hipSetDevice
 int row_length(const zfft_plan *p);  // valid entries per row
+// Rows per frame of L input samples (zfft_plan_segments_per_line): 1 unless 1 <= g < nseg.
+int64_t lines_per_frame(const zfft_plan *p, int64_t L);
 // A NULL stream handle means HIP's default (null) stream, as everywhere in HIP.
 inline hipStream_t pick_stream(zfft_plan *, void *s) { return (hipStream_t)s; }
 

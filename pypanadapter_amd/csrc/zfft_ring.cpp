@@ -26,6 +26,7 @@
 
 #include "zfft.h"
 #include "zfft_internal.h"
+#include "zfft_plan.h"
 
 struct zfft_ring {
   std::mutex mu;
@@ -137,6 +138,9 @@ int zfft_ring_take(zfft_ring *r, const void **frame, int64_t *n, int64_t *total)
 int zfft_ring_process(zfft_ring *r, zfft_plan *plan, float *row_out, int32_t *produced) {
   if (!r || !plan || !row_out || !produced) return zfft::set_error("null argument"), ZFFT_EINVAL;
   *produced = 0;
+  if (plan->seg_per_line >= 1)  // (before a frame is taken: row_out holds one row)
+    return zfft::set_error("the plan has segments_per_line >= 1: a frame gives several rows, use "
+                           "zfft_ring_process_lines"), ZFFT_EINVAL;
   const void *frame = nullptr;
   int64_t n = 0;
   int rc = zfft_ring_take(r, &frame, &n, nullptr);
@@ -148,6 +152,28 @@ int zfft_ring_process(zfft_ring *r, zfft_plan *plan, float *row_out, int32_t *pr
   if (n < c.n_fft) return ZFFT_OK;  // PSD.update skips frames shorter than fft_size (T:1522-1523)
   rc = zfft_process(plan, frame, n, 1, row_out);
   if (rc == ZFFT_OK) *produced = 1;
+  return rc;
+}
+
+int zfft_ring_process_lines(zfft_ring *r, zfft_plan *plan, float *rows_out, int32_t max_lines,
+                            int32_t *produced) {
+  if (!r || !plan || !rows_out || !produced) return zfft::set_error("null argument"), ZFFT_EINVAL;
+  *produced = 0;
+  zfft_config c;
+  int rc = zfft_plan_config(plan, &c);
+  if (rc) return rc;
+  if (c.in_dtype != r->dtype) return zfft::set_error("ring and plan in_dtype differ"), ZFFT_EINVAL;
+  // the line count grows with the frame length: a buffer for the ring's capacity holds any frame
+  if ((int64_t)max_lines < zfft_line_count(r->max_size, c.zoom, c.n_fft, plan->seg_per_line))
+    return zfft::set_error("max_lines is smaller than zfft_line_count(ring capacity = 16 * chunk_size)"),
+           ZFFT_EINVAL;
+  const void *frame = nullptr;
+  int64_t n = 0;
+  rc = zfft_ring_take(r, &frame, &n, nullptr);
+  if (rc) return rc;
+  if (n < c.n_fft) return ZFFT_OK;  // as zfft_ring_process
+  rc = zfft_process(plan, frame, n, 1, rows_out);
+  if (rc == ZFFT_OK) *produced = (int32_t)zfft_line_count(n, c.zoom, c.n_fft, plan->seg_per_line);
   return rc;
 }
 

@@ -47,12 +47,14 @@ class ZoomFFT:
 
     def __init__(self, n_fft: int, zoom: int, fs: float, n_win: int | None = None,
                  window="hamming", f_lo: float = 1.0, scroll: int = 1, device: int = 0,
-                 in_dtype: str = "complex64", flip: bool = False, average: str = "mean"):
+                 in_dtype: str = "complex64", flip: bool = False, average: str = "mean",
+                 segments_per_line: int = 0):
         """in_dtype: "complex64" (complex ndarray), "complex32" (float16 interleaved I,Q,
         shape (..., 2L)), "cu8" (RTL-SDR uint8 interleaved I,Q, value b/127.5 - 1) or "f32"
         (real samples, AudioPan; at zoom 1 the rows are one-sided and `row_length` long).
         flip: reverse every frame on load (the sources' np.flip, S:541-543).
-        average: the Welch detector over a frame's segments, see `set_average`."""
+        average: the Welch detector over a frame's segments, see `set_average`.
+        segments_per_line: Welch segments per waterfall line, see `set_segments_per_line`."""
         self.lib = _lib.load()
         if average not in _lib.AVERAGES:
             raise ValueError(f"average must be one of {sorted(_lib.AVERAGES)}")
@@ -80,6 +82,9 @@ class ZoomFFT:
         self.average = "mean"
         if average != "mean":
             self.set_average(average)
+        self.segments_per_line = 0
+        if segments_per_line:
+            self.set_segments_per_line(segments_per_line)
 
     # ---------------------------------------------------------------- lifetime
     def close(self):
@@ -108,7 +113,7 @@ class ZoomFFT:
     def timings(self) -> list:
         """Per-launch ms of the last process call (needs set_timing(True)), in launch order,
         one per name of `launch_names()`: XA schedule [xa_stage_mix, xa_stage, ..., welch_rows
-        | welch4 (median / max: welch_segs | welch4_segs, then welch_select)]; blocked schedules a forward and a backward pass per stage; a batched host
+        | welch4 (median / max: welch_segs | welch4_segs, then welch_select; with segments_per_line whatever the plan ran for the lines)]; blocked schedules a forward and a backward pass per stage; a batched host
         call repeats the sequence per batch after a "batch_wait" interval."""
         buf = (ctypes.c_float * 1024)()
         n = ctypes.c_int32()
@@ -157,6 +162,33 @@ class ZoomFFT:
         check(self.lib.zfft_plan_average(self._plan, _lib.AVERAGES[average]), "zfft_plan_average")
         self.average = average
 
+    def set_segments_per_line(self, g: int) -> None:
+        """Time-resolved waterfall (zfft_plan_segments_per_line): 0, the default, gives one row
+        per frame; g >= 1 gives `lines(n_samples)` = ceil(nseg / g) rows per frame in time order,
+        each the plan's detector over g consecutive Welch segments (the last over the rest).
+        g = 1 is scipy.signal.spectrogram's columns through the reference's crop and dB;
+        g >= nseg is the one row of g = 0.  Holds for every later call until changed."""
+        check(self.lib.zfft_plan_segments_per_line(self._plan, int(g)), "zfft_plan_segments_per_line")
+        self.segments_per_line = int(g)
+
+    def lines(self, n_samples: int) -> int:
+        """Rows per frame of n_samples input samples (zfft_line_count); 1 at g = 0."""
+        n = self.lib.zfft_line_count(int(n_samples), self.zoom, self.n_fft, self.segments_per_line)
+        if n < 1:
+            raise ValueError(f"zfft_line_count: bad arguments (n_samples {n_samples})")
+        return int(n)
+
+    def line_times(self, n_samples: int) -> np.ndarray:
+        """Centre time of each of the frame's lines, seconds from its first sample
+        (zfft_line_times: scipy.signal.spectrogram's t at the input rate, averaged per line)."""
+        n = self.lines(n_samples)
+        t = np.empty(n, dtype=np.float64)
+        got = ctypes.c_int32()
+        check(self.lib.zfft_line_times(int(n_samples), self.zoom, self.n_fft, self.fs,
+                                       self.segments_per_line, t.ctypes.data_as(ctypes.c_void_p), n,
+                                       ctypes.byref(got)), "zfft_line_times")
+        return t[:got.value]
+
     def set_lo_frames(self, f_lo, frames_per_lo: int = 1) -> None:
         """Batched multi-IF (config 4): frame f of each call is mixed with
         f_lo[(f // frames_per_lo) % len(f_lo)] (the reference's f_demod per IF, S:2090);
@@ -198,29 +230,37 @@ class ZoomFFT:
         return n
 
     def rows(self, frames) -> np.ndarray:
-        """(F, L) or (L,) complex IQ -> (F, W) or (W,) float32 dB rows."""
+        """(F, L) or (L,) complex IQ -> (F, W) or (W,) float32 dB rows; with
+        segments_per_line >= 1, (F, R, W) or (R, W): the R = lines(L) lines of each frame."""
         x = self._as_iq(frames)
         single = x.ndim == 1
         x2 = x.reshape(1, -1) if single else x
         F, L = x2.shape[0], self._samples(x2)
-        out = np.empty((F, self.n_win), dtype=np.float32)
+        by_line = self.segments_per_line >= 1
+        R = self.lines(L) if by_line else 1
+        out = np.empty((F * R, self.n_win), dtype=np.float32)
         check(self.lib.zfft_process(self._plan, x2.ctypes.data_as(ctypes.c_void_p), L, F,
                                     out.ctypes.data_as(ctypes.c_void_p)), "zfft_process")
         n = self.row_length
         if n != self.n_win:  # one-sided rows (real input at zoom 1)
             out = np.ascontiguousarray(out[:, :n])
+        if by_line:
+            out = out.reshape(F, R, -1)
         return out[0] if single else out
 
     def process_host(self, iq_ptr: int, n_samples: int, n_frames: int, rows_ptr: int) -> None:
         """zfft_process on raw host pointers (e.g. a pinned torch tensor's data_ptr()): frames in
-        the plan's input format, rows n_frames * n_win floats.  Synchronous; large inputs go in
+        the plan's input format, rows n_frames * R * n_win floats (R = lines(n_samples); 1 without
+        segments_per_line).  Synchronous; large inputs go in
         batches whose H2D copy overlaps the previous batch's compute."""
         check(self.lib.zfft_process(self._plan, ctypes.c_void_p(iq_ptr), int(n_samples),
                                     int(n_frames), ctypes.c_void_p(rows_ptr)), "zfft_process")
 
     def process_device(self, d_iq_ptr: int, n_samples: int, n_frames: int, d_rows_ptr: int,
                        stream: int = 0) -> None:
-        """Device pointers (e.g. torch .data_ptr()); enqueued on `stream`, no sync."""
+        """Device pointers (e.g. torch .data_ptr()); enqueued on `stream`, no sync.  The row
+        buffer holds n_frames * R * n_win floats (R = lines(n_samples); 1 without
+        segments_per_line) and is taken on trust."""
         check(self.lib.zfft_process_device(self._plan, ctypes.c_void_p(d_iq_ptr), int(n_samples),
                                            int(n_frames), ctypes.c_void_p(d_rows_ptr),
                                            ctypes.c_void_p(stream or None)), "zfft_process_device")
@@ -423,7 +463,15 @@ class IQRing:
 
     def process(self, plan: "ZoomFFT"):
         """PSD.update (T:1513-1548): the next row from the drained frame, or None when the
-        frame is shorter than fft_size (T:1522-1523)."""
+        frame is shorter than fft_size (T:1522-1523).  A plan with segments_per_line >= 1 gives
+        the drained frame's (R, W) lines instead (zfft_ring_process_lines)."""
+        if plan.segments_per_line >= 1:
+            cap = plan.lines(self.max_size)
+            rows = np.empty((cap, plan.n_win), dtype=np.float32)
+            produced = ctypes.c_int32()
+            check(self.lib.zfft_ring_process_lines(self._ring, plan._plan, rows.ctypes.data_as(ctypes.c_void_p),
+                                                   cap, ctypes.byref(produced)), "zfft_ring_process_lines")
+            return np.ascontiguousarray(rows[:produced.value, :plan.row_length]) if produced.value else None
         row = np.empty(plan.n_win, dtype=np.float32)
         produced = ctypes.c_int32()
         check(self.lib.zfft_ring_process(self._ring, plan._plan, row.ctypes.data_as(ctypes.c_void_p),

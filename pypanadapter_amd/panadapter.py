@@ -41,14 +41,15 @@ class PlanCache:
         self.plan: ZoomFFT | None = None
 
     def get(self, fs, n_fft, zoom, n_win, window="hamming", f_lo=1.0,
-            in_dtype="complex64", average="mean") -> ZoomFFT:
+            in_dtype="complex64", average="mean", segments_per_line=0) -> ZoomFFT:
         key = (float(fs), int(n_fft), int(zoom), int(n_win), _key(window), float(f_lo), in_dtype,
-               average)
+               average, int(segments_per_line))
         if key != self._key:
             if self.plan is not None:
                 self.plan.close()
             self.plan = ZoomFFT(n_fft, zoom, fs, n_win=n_win, window=window, f_lo=f_lo,
-                                device=self.device, in_dtype=in_dtype, average=average)
+                                device=self.device, in_dtype=in_dtype, average=average,
+                                segments_per_line=int(segments_per_line))
             self._key = key
         return self.plan
 
@@ -90,6 +91,24 @@ def psd_row(chunk, fs: float, fft_size: int, fft_ratio: int, n_win: int | None =
     plan = _cache(device, purpose).get(fs, fft_size, fft_ratio, n_win, window, f_lo,
                                        "f32" if real else "complex64", average)
     return plan.rows(chunk).astype(np.float64)
+
+
+def psd_lines(chunk, fs: float, fft_size: int, fft_ratio: int, segments_per_line: int,
+              n_win: int | None = None, window="hamming", f_lo: float = 1.0, device: int = 0,
+              average: str = "mean") -> np.ndarray:
+    """The time-resolved form of `psd_row`: (R, n_win) float64, the chunk's lines in time order,
+    each the detector over `segments_per_line` consecutive Welch segments (1: the columns of
+    scipy.signal.spectrogram through the reference's crop and dB) -- what a caller feeds to
+    `Waterfall.image_update` one by one.  R = ceil(nseg / segments_per_line); 0, or a value of
+    at least nseg, gives the one row of `psd_row` as (1, n_win).  Its plan (one per detector,
+    rebuilt when `segments_per_line` or another field changes) is cached apart from `psd_row`'s."""
+    n_win = int(fft_size) // int(fft_ratio) if n_win is None else int(n_win)
+    g = int(segments_per_line)
+    real = not np.iscomplexobj(chunk)
+    plan = _cache(device, f"lines/{average}").get(fs, fft_size, fft_ratio, n_win, window, f_lo,
+                                                       "f32" if real else "complex64", average, g)
+    rows = plan.rows(chunk).astype(np.float64)
+    return rows.reshape(-1, rows.shape[-1])
 
 
 def thread_psd_row(chunk, fs: float, fft_size: int, fft_ratio: int, window="hamming",
