@@ -1,4 +1,4 @@
-// Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp,
+// Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
 // zfft_waterfall.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
 // (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip).  Not part of the C-ABI.
 #pragma once
@@ -9,10 +9,11 @@
 #include <string>
 #include <vector>
 
+#include "zfft_welch_plan.h"  // the Welch forms' domains (kMaxLdsFft, kDifMin / kDifMax, ...), WelchSel
+
 namespace zfft {
 
 constexpr int kPad = 27;      // sosfiltfilt odd-extension length (3 * ntaps)
-constexpr int kMaxLdsFft = 16384;
 
 // float32 copy of the ↓2 Chebyshev-I SOS cascade (cheby1_q2.h); passed by value as a
 // kernel argument so every coefficient lives in SGPRs.
@@ -329,15 +330,11 @@ struct WelchLines {
   int grp = 0, lines = 1;
   float scale_tail = 0.f;
 };
-// DIF Welch split for a call of `frames` frames: enough workgroups for the chip (about 768 at
-// N = 4096), at least two segments each; 1 for full batches.
-int welch_dif_split(int n_fft, int nseg, int frames);
-// The same for fused mean lines: parts of whole lines, every part at least one line.
-int welch_dif_split_lines(int n_fft, int lines, int frames);
 
 // segs (median / max detectors, zfft_plan_average): instead of the dB rows, every segment's
 // scaled linear bins into rows[(f nseg + s) n_win + j] (g.scale then without 1/nseg; the split
 // form writes them at their absolute s and needs neither g.parts nor a second launch).
+// g.split is welch_split's (zfft_welch_plan.h).
 hipError_t launch_welch_rows(const float2 *x, int64_t len, const float *win, const float2 *tw,
                              const WelchGeom &g, float *rows, int frames, hipStream_t st,
                              bool segs = false, const WelchLines &ln = WelchLines());
@@ -363,7 +360,9 @@ struct WelchSelect {
   int grp = 0, lines = 1;
   float inv_bias_tail = 1.f;
 };
-hipError_t launch_welch_select(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st);
+// form: how the keys are held (choose_welch's; refused where it does not fit g).
+hipError_t launch_welch_select(const float *seg, WelchSelect g, WelchSel form, float *rows, int frames,
+                               hipStream_t st);
 
 hipError_t launch_waterfall_init(float *ring, int H, int W, hipStream_t st);
 hipError_t launch_waterfall_push(float *ring, int H, int W, const float *rows,

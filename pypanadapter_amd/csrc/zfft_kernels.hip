@@ -991,7 +991,6 @@ __global__ void __launch_bounds__(256) welch_parts_kernel(const float *__restric
 #undef DIF_X
 #undef DIF_W
 
-constexpr int kDifMinSplit = 1024;
 template <int N, bool SEG, bool LINES = false>
 static hipError_t welch_dif_launch(const float2 *x, int64_t len, const float *win, const float2 *tw,
                                    const WelchGeom &g, float *rows, int frames, hipStream_t st,
@@ -1028,28 +1027,6 @@ static hipError_t welch_dif_launch(const float2 *x, int64_t len, const float *wi
                        st, (const float *)g.parts, g, rows);
   }
   return hipGetLastError();
-}
-
-int welch_dif_split(int n_fft, int nseg, int frames) {
-  if (n_fft < kDifMinSplit || n_fft > 16384 || nseg < 4) return 1;
-  const int fpb = n_fft / 16 >= 256 ? 1 : 256 / (n_fft / 16);
-  const int blocks = (frames + fpb - 1) / fpb;
-  const int target = 768 * 256 / std::max(256, n_fft / 16);  // workgroups that fill the chip
-  if (blocks >= target / 2) return 1;
-  const int want = std::min((target + blocks - 1) / blocks, nseg / 2);
-  const int per = (nseg + want - 1) / want;
-  return (nseg + per - 1) / per;  // every part non-empty
-}
-
-int welch_dif_split_lines(int n_fft, int lines, int frames) {
-  if (n_fft < kDifMinSplit || n_fft > 16384 || lines < 2) return 1;
-  const int fpb = n_fft / 16 >= 256 ? 1 : 256 / (n_fft / 16);
-  const int blocks = (frames + fpb - 1) / fpb;
-  const int target = 768 * 256 / std::max(256, n_fft / 16);  // workgroups that fill the chip
-  if (blocks >= target / 2) return 1;
-  const int want = std::min((target + blocks - 1) / blocks, lines);
-  const int lpp = (lines + want - 1) / want;
-  return (lines + lpp - 1) / lpp;  // every part holds at least one line
 }
 
 // ------------------------------------------------------------------ Welch row, four-step
@@ -1288,7 +1265,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZFFT_W4_RWP
 //        cfg1's 127 segments are 32 KB, five waves per CU) -- written and read by the same
 //        thread, no barrier,
 //   else re-read from the scratch each step (L2); max needs one pass and takes this form.
-constexpr int kSelLdsSegs = 256;  // 64 KB of LDS per wave at most
+// Which one: choose_welch's WelchSel (zfft_welch_plan.h, with kSelRegSegs and kSelLdsSegs).
+static_assert(kSelRegSegs == 32 && kSelLdsSegs * 256 <= 64 * 1024, "largest register form; 64 KB of LDS per wave");
 constexpr uint32_t kSelInf = 0x7f800000u;
 __device__ __forceinline__ uint32_t sel_key(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 
@@ -1751,12 +1729,9 @@ static hipError_t welch_launch_t(const float2 *x, int64_t len, const float *win,
   return hipGetLastError();
 }
 
-// the in-place DIF kernel covers 1024 <= N <= 16384 (N = 16384: one 1024-thread frame per
-// workgroup, 139 KB of LDS, a 4-value prefetch to stay within 128 VGPRs)
-#ifndef ZFFT_DIF_MAX
-#define ZFFT_DIF_MAX 16384
-#endif
-constexpr int kDifMin = 1024, kDifMax = ZFFT_DIF_MAX;
+// the in-place DIF kernel's domain kDifMin .. kDifMax (zfft_welch_plan.h): the sizes of this switch
+static_assert(kDifMin == 1024 && kDifMax <= 16384 && kMaxLdsFft == 16384,
+              "zfft_welch_plan.h mirrors the Welch kernels' sizes");
 template <int R0, bool SEG, bool LINES>
 static hipError_t welch_launch(const float2 *x, int64_t len, const float *win, const float2 *tw,
                                const WelchGeom &g, float *rows, int frames, hipStream_t st,
@@ -1799,7 +1774,8 @@ hipError_t launch_welch_rows(const float2 *x, int64_t len, const float *win, con
         g.split < 1 || g.split > ln.lines)
       return hipErrorInvalidValue;
     const bool dif = g.n_fft >= kDifMin && g.n_fft <= kDifMax;
-    const int lpp = (ln.lines + g.split - 1) / g.split;  // (an empty part would read past its frame)
+    // welch_split's invariant: every part starts inside its frame (an empty one would read past it)
+    const int lpp = (ln.lines + g.split - 1) / g.split;
     if (!dif || (g.split - 1) * lpp >= ln.lines) return hipErrorInvalidValue;
     return welch_rows_by_radix<false, true>(x, len, win, tw, g, rows, frames, st, ln);
   }
@@ -1878,23 +1854,28 @@ hipError_t launch_welch4(const float2 *x, int64_t len, const float *win, const f
 }
 
 template <bool LINES>
-static hipError_t welch_select_go(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st) {
+static hipError_t welch_select_go(const float *seg, WelchSelect g, WelchSel form, float *rows, int frames,
+                                  hipStream_t st) {
   // keys per column: the frame's segments, or (LINES) those of a full line; vf: columns of j
   const int keys = LINES ? g.grp : g.nseg;
   const int64_t vf = (int64_t)frames * (LINES ? g.lines : 1);
-  const bool reg = keys <= 32;
-  g.jblocks = (g.row_len + (reg ? 255 : 63)) / (reg ? 256 : 64);
+  // register slots of the form: 4, 8, 16, 24, 32 (0: none)
+  const int ns = form == WelchSel::Reg4 ? 4 : form == WelchSel::Reg8 ? 8 : form == WelchSel::Reg16 ? 16
+                 : form == WelchSel::Reg24 ? 24 : form == WelchSel::Reg32 ? 32 : 0;
+  if (ns ? keys > ns : form == WelchSel::Lds ? (g.mode != 1 || keys > kSelLdsSegs) : form != WelchSel::Scratch)
+    return hipErrorInvalidValue;
+  g.jblocks = (g.row_len + (ns ? 255 : 63)) / (ns ? 256 : 64);
   if (vf * g.jblocks > INT32_MAX) return hipErrorInvalidValue;
   const dim3 grid((unsigned)(vf * g.jblocks));
-  if (reg) {
+  if (ns) {
 #define SEL_REG(NS) hipLaunchKernelGGL((welch_select_reg_kernel<NS, LINES>), grid, dim3(256), 0, st, seg, g, rows)
-    if (keys <= 4) SEL_REG(4);
-    else if (keys <= 8) SEL_REG(8);
-    else if (keys <= 16) SEL_REG(16);
-    else if (keys <= 24) SEL_REG(24);
+    if (ns == 4) SEL_REG(4);
+    else if (ns == 8) SEL_REG(8);
+    else if (ns == 16) SEL_REG(16);
+    else if (ns == 24) SEL_REG(24);
     else SEL_REG(32);
 #undef SEL_REG
-  } else if (g.mode == 1 && keys <= kSelLdsSegs) {  // (max is the first pass alone: no LDS)
+  } else if (form == WelchSel::Lds) {
     static bool attr = false;
     if (!attr) {
       const hipError_t e = hipFuncSetAttribute((const void *)welch_select_lds_kernel<LINES>,
@@ -1909,16 +1890,18 @@ static hipError_t welch_select_go(const float *seg, WelchSelect g, float *rows, 
   return hipGetLastError();
 }
 
-hipError_t launch_welch_select(const float *seg, WelchSelect g, float *rows, int frames, hipStream_t st) {
+hipError_t launch_welch_select(const float *seg, WelchSelect g, WelchSel form, float *rows, int frames,
+                               hipStream_t st) {
   if (g.nseg < 1 || g.row_len < 1 || g.row_len > g.n_win || frames < 1) return hipErrorInvalidValue;
   if (g.grp == 0) {
     if (g.mode != 1 && g.mode != 2) return hipErrorInvalidValue;
-    return welch_select_go<false>(seg, g, rows, frames, st);
+    return welch_select_go<false>(seg, g, form, rows, frames, st);
   }
   // lines: 1 <= grp < nseg, lines = ceil(nseg / grp); mode 0 (mean) has its own kernel
-  if (g.grp < 1 || g.grp >= g.nseg || g.lines != (g.nseg + g.grp - 1) / g.grp || g.mode < 0 || g.mode > 2)
+  if (g.grp < 1 || g.grp >= g.nseg || g.lines != (g.nseg + g.grp - 1) / g.grp || g.mode < 0 || g.mode > 2 ||
+      (g.mode == 0) != (form == WelchSel::MeanLines))
     return hipErrorInvalidValue;
-  if (g.mode != 0) return welch_select_go<true>(seg, g, rows, frames, st);
+  if (g.mode != 0) return welch_select_go<true>(seg, g, form, rows, frames, st);
   g.jblocks = (g.row_len + 255) / 256;
   const int64_t blocks = (int64_t)frames * g.lines * g.jblocks;
   if (blocks > INT32_MAX) return hipErrorInvalidValue;

@@ -1,7 +1,8 @@
 // zfft_plan.cpp -- the plan of libzfft.so: create / destroy, its settings, the stream ordering
-// helpers, the Welch launch and the host entry points (zfft_process, zfft_decimate).  The
-// plan object is in zfft_plan.h, the decimator in zfft_decim.cpp (schedule choice:
-// zfft_schedule.cpp), the waterfall in zfft_waterfall.cpp.
+// helpers and the host entry points (zfft_process, zfft_decimate).  The plan object is in
+// zfft_plan.h, the decimator in zfft_decim.cpp (schedule choice: zfft_schedule.cpp), the Welch
+// launches in zfft_welch.cpp (form choice: zfft_welch_plan.cpp), the waterfall in
+// zfft_waterfall.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,9 +13,9 @@
 
 #include "cheby1_q2.h"
 #include "zfft.h"
-#include "zfft_median_bias.h"
 #include "zfft_plan.h"
 #include "zfft_schedule.h"
+#include "zfft_welch_plan.h"
 
 namespace zfft {
 
@@ -87,9 +88,6 @@ int enter(zfft_plan *p) {
   return ZFFT_OK;
 }
 
-// Real input at zoom 1 takes scipy.signal.welch's one-sided branch.
-static bool onesided(const zfft_plan *p) { return p->cfg.in_dtype == kInF32R && p->K == 0; }
-
 // The length of the reference's slice fftshift(P)[N//2 - W//2 : N//2 + W//2] (S:2114):
 // 2 (W//2), or in the one-sided case that slice of the N/2+1 bins.
 int row_length(const zfft_plan *p) {
@@ -117,73 +115,6 @@ int ilog2(int64_t v) {
   return r;
 }
 
-#ifndef ZFFT_WELCH_ONEWG_MAX
-#define ZFFT_WELCH_ONEWG_MAX 16384
-#endif
-constexpr int kWelchOneWgMax = ZFFT_WELCH_ONEWG_MAX;  // auto Welch: one workgroup per frame up to here
-
-// In-place radix-2 DFT (forward, exp(-2 pi i k n / N)), N a power of two, float64.
-void fft64(std::vector<double> &re, std::vector<double> &im) {
-  const size_t n = re.size();
-  for (size_t i = 1, j = 0; i < n; ++i) {
-    size_t bit = n >> 1;
-    for (; j & bit; bit >>= 1) j ^= bit;
-    j |= bit;
-    if (i < j) std::swap(re[i], re[j]), std::swap(im[i], im[j]);
-  }
-  for (size_t len = 2; len <= n; len <<= 1) {
-    const double a = -2.0 * M_PI / (double)len;
-    for (size_t i = 0; i < n; i += len)
-      for (size_t k = 0; k < len / 2; ++k) {
-        const double c = std::cos(a * (double)k), sn = std::sin(a * (double)k);
-        const size_t u = i + k, v = u + len / 2;
-        const double tr = re[v] * c - im[v] * sn, ti = re[v] * sn + im[v] * c;
-        re[v] = re[u] - tr, im[v] = im[u] - ti;
-        re[u] += tr, im[u] += ti;
-      }
-  }
-}
-
-// welch builds get_window(window, nperseg); nperseg = min(N, L_d) (short-input branch).
-int ensure_window(zfft_plan *p, int nperseg) {
-  if (p->win_len == nperseg) return ZFFT_OK;
-  int rc = quiesce(p);
-  if (rc) return rc;
-  std::vector<double> w;
-  if (p->cfg.window_kind == ZFFT_WIN_ARRAY) {
-    if (nperseg != p->cfg.n_fft)
-      return fail(ZFFT_EINVAL, "window is longer than input signal (array window of length "
-                               "n_fft, decimated frame shorter than n_fft)");
-    w.assign(p->user_window.begin(), p->user_window.end());
-  } else if (!make_window(p->cfg.window_kind, p->cfg.window_param, nperseg, w)) {
-    return fail(ZFFT_EINVAL, "window generation failed");
-  }
-  std::vector<float> wf(nperseg);
-  double ss = 0.0;
-  for (int i = 0; i < nperseg; ++i) {
-    wf[i] = (float)w[i];
-    ss += w[i] * w[i];
-  }
-  hipError_t e = p->win.ensure(p->cfg.n_fft * sizeof(float));
-  if (e != hipSuccess) return fail(ZFFT_ENOMEM, "window allocation failed");
-  e = hipMemcpy(p->win.p, wf.data(), nperseg * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return hip_fail(e, "window upload");
-  if (nperseg == p->cfg.n_fft && p->cfg.n_fft >= 4096) {  // (four-step capable sizes)
-    // the four-step Welch subtracts the segment mean after its transform: X = FFT(x w) -
-    // mean FFT(w) (scipy's detrend='constant' is linear); FFT(w) of the float32 window, fp64
-    std::vector<double> re(wf.begin(), wf.end()), im(nperseg, 0.0);
-    fft64(re, im);
-    std::vector<float2> wft(nperseg);
-    for (int k = 0; k < nperseg; ++k) wft[k] = make_float2((float)re[k], (float)im[k]);
-    e = p->winf.ensure(nperseg * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpy(p->winf.p, wft.data(), nperseg * sizeof(float2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail(e, "window transform upload");
-  }
-  p->win_len = nperseg;
-  p->win_ss = ss;
-  return ZFFT_OK;
-}
-
 int check_lengths(const zfft_plan *p, int64_t L, int32_t frames, std::vector<int64_t> &n) {
   if (L < 1 || frames < 1) return fail(ZFFT_EINVAL, "n_samples and n_frames must be >= 1");
   if (L > (int64_t)1 << 30) return fail(ZFFT_EINVAL, "n_samples too large (max 2^30)");
@@ -196,18 +127,6 @@ int check_lengths(const zfft_plan *p, int64_t L, int32_t frames, std::vector<int
   return ZFFT_OK;
 }
 
-#ifndef ZFFT_WELCH4_CHUNK_MB
-#define ZFFT_WELCH4_CHUNK_MB 0  // chunks of 48/96/192 MB measured 3.1x/1.8x/1.4x slower (cfg5)
-#endif
-constexpr size_t kWelch4ChunkBytes = (size_t)ZFFT_WELCH4_CHUNK_MB << 20;  // 0: one launch set
-// Segment scratch of the median / max detectors per chunk of frames.  A cap of the Infinity
-// Cache's size (256 MB, so that welch_select reads what the Welch kernels just wrote) measured
-// slower than one launch set wherever it splits a call (cfg1's 4096 frames, 532 MB: 2.95 against
-// 2.61 ms), so the cap only bounds the workspace.
-#ifndef ZFFT_AVG_SCRATCH_MB
-#define ZFFT_AVG_SCRATCH_MB 1024
-#endif
-constexpr size_t kAvgScratchBytes = (size_t)ZFFT_AVG_SCRATCH_MB << 20;
 constexpr int kMaxLoRows = 256;  // LO rows of set_lo_frames (each n_samples x 8 B)
 // zfft_process pipelining: inputs of >= 64 MB go in batches of about 1 GB (at least two).
 constexpr size_t kPipeMinBytes = (size_t)64 << 20;
@@ -230,10 +149,6 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
   int rc = check_lengths(p, L, frames, n);
   if (rc) return rc;
   const int64_t Ld = n[p->K];
-  const int N = p->cfg.n_fft;
-  const int nperseg = (int)(Ld < N ? Ld : N);
-  rc = ensure_window(p, nperseg);
-  if (rc) return rc;
   if (p->K > 0) {  // the LO rows exist (and have their stride) before input_of reads it
     rc = ensure_lo(p, L);
     if (rc) return rc;
@@ -252,117 +167,9 @@ int process_device(zfft_plan *p, const void *d_iq, int64_t L, int32_t frames, fl
     mark(p, st, "ingest");
     x = p->dec.as<float2>();
   }
-  WelchGeom w;
-  w.n_fft = N;
-  w.log2n = ilog2(N);
-  w.n_win = p->cfg.n_win;
-  w.nperseg = nperseg;
-  w.step = nperseg - nperseg / 2;
-  w.nseg = (int)((Ld - nperseg) / w.step + 1);
-  // density scaling 1/(fs*sum(w^2)) and the segment mean (csd average='mean'); the median and
-  // max detectors (zfft_plan_average) take the segments' densities one by one
-  // lines (zfft_plan_segments_per_line, 1 <= g < nseg): R rows per frame, every detector (mean
-  // too) reduced per group of g segments from the segment scratch
-  const int G = p->seg_per_line >= 1 && p->seg_per_line < w.nseg ? p->seg_per_line : 0;
-  const int R = G ? (w.nseg + G - 1) / G : 1;
-  // auto: four-step above 16384 (the only form there); N <= 16384 runs one workgroup per
-  // frame (the in-place DIF kernel from N = 1024)
-  const bool four = p->welch == 2 || (p->welch == 0 && N > kWelchOneWgMax);
-  // mean lines from the in-place DIF kernel are fused (its LINES variant writes each line from
-  // the segment loop: faster than the scratch route at every g measured);
-  // median, max, N < 1024 (the fused Stockham form measured slower) and the four-step form
-  // reduce the segment scratch
-  const bool fused = G > 0 && p->average == ZFFT_AVG_MEAN && !four && N >= 1024 && N <= kMaxLdsFft &&
-                     p->lines_route != 1;
-  const bool segs = (p->average != ZFFT_AVG_MEAN || G > 0) && !fused;
-  WelchLines ln;
-  if (fused) {
-    ln.grp = G;
-    ln.lines = R;
-    ln.scale_tail = (float)(1.0 / (p->cfg.fs * p->win_ss * (double)(w.nseg - (R - 1) * G)));
-  }
-  w.scale = (float)(1.0 / (p->cfg.fs * p->win_ss * (segs ? 1.0 : fused ? (double)G : (double)w.nseg)));
-  if (onesided(p)) {
-    w.onesided = 1;
-    w.row_a = N / 2 - p->cfg.n_win / 2;
-    w.row_len = row_length(p);
-  }
-  // floats per frame a Welch launch writes: the row (fused lines: R rows), or (segs) every
-  // segment's bins
-  const int64_t ostride = (int64_t)(segs ? w.nseg : R) * p->cfg.n_win;
-  // the Welch launches of nf frames from xc: dB rows into out, or (segs) the segments' bins
-  auto welch = [&](const float2 *xc, float *out, int nf) -> int {
-    hipError_t e;
-    if (four) {
-      // frames in chunks whose intermediate Z (nseg x N complex64 per frame) stays in the
-      // 256 MB Infinity Cache between the column and the row pass instead of round-tripping
-      // through HBM
-      const size_t zf = (size_t)w.nseg * N * sizeof(float2);
-      const int chunk = kWelch4ChunkBytes > 0
-                            ? (int)std::max<size_t>(1, std::min<size_t>(nf, kWelch4ChunkBytes / zf))
-                            : nf;
-      w.fused_mean = nperseg == N ? 1 : 0;  // partial sums from the column pass (kN2-column groups)
-      e = p->means.ensure((size_t)chunk * w.nseg * std::max(1, N / 256 / 16) * sizeof(float2));
-      if (e == hipSuccess) e = p->z4.ensure((size_t)chunk * zf);
-      if (e != hipSuccess) return fail(ZFFT_ENOMEM, "four-step Welch workspace allocation failed");
-      for (int f0 = 0; f0 < nf; f0 += chunk) {
-        const int nc = std::min(chunk, nf - f0);
-        e = launch_welch4(xc + (int64_t)f0 * Ld, Ld, p->win.as<float>(), p->tw.as<float2>(),
-                          p->tws.as<float2>(), w.fused_mean ? p->winf.as<float2>() : nullptr, w,
-                          p->means.as<float2>(), p->z4.as<float2>(), out + (int64_t)f0 * ostride, nc, st,
-                          segs);
-        if (e != hipSuccess) return hip_fail(e, "welch4 launch");
-      }
-    } else {
-      // few frames per call (the reference's one): each frame's segments over several
-      // workgroups (welch_dif_split), partial PSDs summed by a second launch
-      w.split = nperseg != N ? 1 : fused ? welch_dif_split_lines(N, R, nf) : welch_dif_split(N, w.nseg, nf);
-      p->last_split = w.split;
-      if (w.split > 1 && !segs && !fused) {
-        e = p->wparts.ensure((size_t)nf * w.split * p->cfg.n_win * sizeof(float));
-        if (e != hipSuccess) return fail(ZFFT_ENOMEM, "Welch workspace allocation failed");
-        w.parts = p->wparts.as<float>();
-      }
-      e = launch_welch_rows(xc, Ld, p->win.as<float>(), p->tw.as<float2>(), w, out, nf, st, segs, ln);
-      if (e != hipSuccess) return hip_fail(e, "welch_rows launch");
-    }
-    return ZFFT_OK;
-  };
-  if (!segs) {
-    rc = welch(x, d_rows, frames);
-    if (rc) return rc;
-    mark(p, st, fused ? "welch_lines" : four ? "welch4" : "welch_rows");
-  } else {
-    // the frames in chunks whose segment scratch stays within the cap; at least one frame
-    const size_t per = (size_t)ostride * sizeof(float);
-    const size_t cap = p->avg_cap ? p->avg_cap : kAvgScratchBytes;
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)frames, cap / per));
-    if (p->wsegs.ensure((size_t)chunk * per) != hipSuccess)
-      return fail(ZFFT_ENOMEM, "Welch segment workspace allocation failed");
-    WelchSelect sel{w.nseg, p->cfg.n_win, row_length(p), p->average,
-                    p->average == ZFFT_AVG_MEDIAN ? (float)(1.0 / median_bias(w.nseg)) : 1.f};
-    if (G) {  // per line: its own segment count n_r (G, or the tail's) in the bias and the mean
-      const int tail = w.nseg - (R - 1) * G;
-      auto inv = [&](int n) {
-        return p->average == ZFFT_AVG_MEDIAN ? (float)(1.0 / median_bias(n))
-               : p->average == ZFFT_AVG_MEAN ? (float)(1.0 / (double)n) : 1.f;
-      };
-      sel.grp = G;
-      sel.lines = R;
-      sel.inv_bias = inv(G);
-      sel.inv_bias_tail = inv(tail);
-    }
-    for (int f0 = 0; f0 < frames; f0 += chunk) {
-      const int nf = std::min(chunk, frames - f0);
-      rc = welch(x + (int64_t)f0 * Ld, p->wsegs.as<float>(), nf);
-      if (rc) return rc;
-      mark(p, st, four ? "welch4_segs" : "welch_segs");
-      const hipError_t e = launch_welch_select(p->wsegs.as<float>(), sel, d_rows + (int64_t)f0 * R * p->cfg.n_win, nf, st);
-      if (e != hipSuccess) return hip_fail(e, "welch_select launch");
-      mark(p, st, G && p->average == ZFFT_AVG_MEAN ? "welch_lines" : "welch_select");
-    }
-  }
-  p->last_row = d_rows + ((int64_t)frames * R - 1) * p->cfg.n_win;
+  rc = run_welch(p, x, Ld, frames, d_rows, st);
+  if (rc) return rc;
+  p->last_row = d_rows + ((int64_t)frames * lines_per_frame(p, L) - 1) * p->cfg.n_win;
   return ZFFT_OK;
 }
 
@@ -398,6 +205,28 @@ extern "C" int zfft__schedule(int32_t zoom, int32_t in_dtype, int32_t path, int6
   const Schedule s = choose_schedule({ilog2(zoom), (int)in_elem_bytes(in_dtype), path, L, frames});
   std::snprintf(name, (size_t)cap, "%s", schedule_name(s));
   return s.rc;
+}
+
+// Test hook (not part of include/zfft.h; needs no device): the Welch form a call of `frames`
+// frames of L samples takes on a plan of these settings -- choose_welch's rc, and one line naming
+// everything that selects a kernel or a grid into desc[cap], e.g.
+// "dif parts split=3 last_split=3 lines=1 chunk=2 select=none".
+extern "C" int zfft__welch_plan(int32_t n_fft, int32_t n_win, int32_t zoom, int32_t in_dtype, int32_t welch,
+                                int32_t average, int32_t seg_per_line, int32_t lines_route, int64_t cap_bytes,
+                                int64_t L, int32_t frames, char *desc, int32_t cap) {
+  if (!is_pow2(n_fft) || n_fft < 32 || n_fft > 65536 || n_win < 2 || n_win > n_fft || !is_pow2(zoom) ||
+      zoom > 512 || in_dtype < kInC64 || in_dtype > kInF32R || average < ZFFT_AVG_MEAN || average > ZFFT_AVG_MAX ||
+      seg_per_line < 0 || lines_route < 0 || lines_route > 1 || cap_bytes < 0 || L < 1 ||
+      L > (int64_t)1 << 30 || frames < 1 || !desc || cap < 1)
+    return ZFFT_EINVAL;
+  const WelchPlan w = choose_welch({n_fft, n_win, zfft_decimated_length(L, zoom), frames,
+                                    welch, average, seg_per_line, lines_route, (size_t)cap_bytes});
+  if (w.rc)
+    std::snprintf(desc, (size_t)cap, "refused");
+  else
+    std::snprintf(desc, (size_t)cap, "%s %s split=%d last_split=%d lines=%d chunk=%d select=%s", welch_fft_name(w.fft),
+                  welch_out_name(w.out), w.split, w.split_last, w.lines, w.chunk, welch_sel_name(w.sel));
+  return w.rc;
 }
 
 extern "C" {
@@ -571,12 +400,10 @@ int zfft_plan_set_lo_frames(zfft_plan *p, const double *f_lo, int32_t n, int32_t
 }
 
 int zfft_plan_welch(zfft_plan *p, int32_t mode) {
-  if (!p || mode < 0 || mode > 2)
-    return fail(ZFFT_EINVAL, "welch mode must be 0 (auto), 1 (one workgroup) or 2 (four-step)");
-  if (mode == 1 && p->cfg.n_fft > kMaxLdsFft)
-    return fail(ZFFT_EUNSUPPORTED, "one-workgroup Welch holds at most 16384 points in LDS");
-  if (mode == 2 && p->cfg.n_fft < 4096)
-    return fail(ZFFT_EINVAL, "four-step Welch needs n_fft >= 4096 (N1 = n_fft/256 >= 16)");
+  if (!p) return fail(ZFFT_EINVAL, "null plan");
+  const char *why;
+  const int rc = welch_mode_rc(p->cfg.n_fft, mode, &why);
+  if (rc) return fail(rc, why);
   p->welch = mode;
   return ZFFT_OK;
 }
@@ -592,9 +419,7 @@ int64_t zfft_line_count(int64_t n_samples, int32_t zoom, int32_t n_fft, int32_t 
   if (n_samples < 1 || n_fft < 2 || g < 0) return -1;
   const int64_t Ld = zfft_decimated_length(n_samples, zoom);
   if (Ld < 1) return -1;
-  if (g == 0 || Ld < n_fft) return 1;  // (short input: one segment of L_d samples)
-  const int64_t nseg = (Ld - n_fft) / (n_fft - n_fft / 2) + 1;
-  return g >= nseg ? 1 : (nseg + g - 1) / g;
+  return welch_segments(Ld, n_fft, g).lines;  // (short input: one segment of L_d samples, one line)
 }
 
 int zfft_line_times(int64_t n_samples, int32_t zoom, int32_t n_fft, double fs, int32_t g, double *t_out,
@@ -608,15 +433,12 @@ int zfft_line_times(int64_t n_samples, int32_t zoom, int32_t n_fft, double fs, i
   if (R > INT32_MAX) return fail(ZFFT_EINVAL, "line_times: too many lines");
   *count = (int32_t)R;
   if (max < R) return fail(ZFFT_EINVAL, "line_times: max is smaller than zfft_line_count");
-  const int64_t Ld = zfft_decimated_length(n_samples, zoom);
-  const int64_t nper = Ld < n_fft ? Ld : n_fft, step = nper - nper / 2;
-  const int64_t nseg = (Ld - nper) / step + 1;
-  const int64_t G = R == 1 ? nseg : g;
+  const WelchSegments s = welch_segments(zfft_decimated_length(n_samples, zoom), n_fft, g);
   for (int64_t r = 0; r < R; ++r) {
-    // the mean of t_s over s = r G .. r G + n - 1: its middle segment (a half step when n is even)
-    const int64_t s0 = r * G, n = std::min(G, nseg - s0);
+    // the mean of t_s over line r's n segments from s0: its middle segment (a half step when n is even)
+    const int64_t s0 = r * s.grp, n = r < R - 1 ? s.grp : s.tail;
     const double mid = (double)s0 + 0.5 * (double)(n - 1);
-    t_out[r] = (mid * (double)step + 0.5 * (double)nper) * (double)zoom / fs;
+    t_out[r] = (mid * (double)s.step + 0.5 * (double)s.nperseg) * (double)zoom / fs;
   }
   return ZFFT_OK;
 }

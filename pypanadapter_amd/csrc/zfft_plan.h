@@ -1,5 +1,5 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
-// (zfft_plan.cpp, zfft_decim.cpp, zfft_waterfall.cpp).  Not part of the C-ABI.
+// (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -73,8 +73,9 @@ struct zfft_plan {
                 // 3 XA tiles (all-pole + FIR + half-rate all-pole), 4 PC tiles (polyphase
                 // cascade; zoom 2, 4, 8 and the head of zoom >= 16), 5 PC walk (one workgroup
                 // per frame; zoom 2: the tiles), 6 FC (fast convolution at zoom 4, 8 and the
-                // head; where FC does not fit, as 5) -- zfft_schedule.h choose_schedule
-  int welch = 0;  // 0 auto, 1 one workgroup per frame, 2 four-step
+                // head; where FC does not fit, as 5), 7 FC at zoom 2 and for the tails of
+                // zoom >= 16 too (else as 6) -- zfft_schedule.h choose_schedule
+  int welch = 0;  // 0 auto, 1 one workgroup per frame, 2 four-step -- zfft_welch_plan.h choose_welch
   DevBuf edge, xk, xa_tab, tws, means, z4, winf;
   DevBuf pc_tab, pc_edge;  // PC decimator: PcTab; all nine frame-end maps of pc_edge_maps.h
                            // (floats), uploaded once
@@ -141,6 +142,8 @@ int done_on(zfft_plan *p, hipStream_t st);
 // overwrites a table that work may still read).
 int quiesce(zfft_plan *p);
 int enter(zfft_plan *p);  // null check + hipSetDevice
+// Real input at zoom 1 takes scipy.signal.welch's one-sided branch.
+inline bool onesided(const zfft_plan *p) { return p->cfg.in_dtype == kInF32R && p->K == 0; }
 int row_length(const zfft_plan *p);  // valid entries per row
 // Rows per frame of L input samples (zfft_plan_segments_per_line): 1 unless 1 <= g < nseg.
 int64_t lines_per_frame(const zfft_plan *p, int64_t L);
@@ -155,5 +158,10 @@ int ensure_lo(zfft_plan *p, int64_t L);
 // schedule choose_schedule gives; *out = the decimated frames, natural layout.
 int run_decimator(zfft_plan *p, const InDesc &in, int64_t L, int frames,
                   const std::vector<int64_t> &n, const float2 **out, hipStream_t st);
+
+// --- zfft_welch.cpp ---
+// The Welch rows (or lines) of `frames` decimated frames of Ld samples at x into d_rows, by the
+// form choose_welch gives; builds the window tables on first use.
+int run_welch(zfft_plan *p, const float2 *x, int64_t Ld, int frames, float *d_rows, hipStream_t st);
 
 }  // namespace zfft

@@ -10,6 +10,7 @@ import pytest
 
 from conftest import (GOLDEN, assert_row_close, case_input, check_rel, golden_cases, golden_rows,
                       row_errors, window_of)
+from welch_plan_check import assert_plan_ran
 
 pytestmark = pytest.mark.gpu
 CASES = golden_cases()["cases"]
@@ -294,14 +295,17 @@ def test_welch_one_workgroup_forms_vs_oracle(oracle_lib, N, z, W, F):
                                       (2048, 1, 2047, 100003), (8192, 8, 1024, 1048576), (4096, 1, 1000, 40960)])
 def test_welch_split_few_frames_vs_oracle(oracle_lib, N, z, W, L):
     """A call of one or two frames -- the reference's use -- splits each frame's segments over
-    several workgroups (welch_dif_split) and sums their partial PSDs in a second launch:
+    several workgroups (welch_split) and sums their partial PSDs in a second launch:
     rows within the gate (pruned and full last stage, odd W, zoom 1), identical on a repeat."""
     from pypanadapter_amd import ZoomFFT
     for F in (1, 2):
         x = _frames(F, L, N, z, W, seed0=9300 + N + z + F)
         with ZoomFFT(N, z, 2.4e6, n_win=W) as plan:
+            plan.set_timing(True)
             rows = plan.rows(x)
+            assert " parts " in assert_plan_ran(plan, L, F)
             again = plan.rows(x)
+            assert_plan_ran(plan, L, F)
         np.testing.assert_array_equal(rows, again)
         for f in range(F):
             assert_row_close(rows[f], oracle_lib.psd_row(x[f], 2.4e6, N, z, W), f"N={N} z={z} F={F} frame {f}")

@@ -12,6 +12,7 @@ import pytest
 
 import welch_average_ref as war
 from conftest import assert_row_close, row_errors
+from welch_plan_check import assert_plan_ran
 
 pytestmark = pytest.mark.gpu
 FS = war.FS
@@ -95,6 +96,8 @@ def test_detectors_vs_float64_reference(oracle_lib, name):
         for average in MODES:
             plan.set_average(average)
             rows = plan.rows(x)
+            desc = assert_plan_ran(plan, L, F, welch=opt.get("welch", 0))
+            assert desc.startswith("four ") == bool(opt.get("four")), desc
             names = plan.launch_names()
             splits[average] = split(plan._plan)
             if average == "mean":
@@ -118,9 +121,11 @@ def test_short_input_branch_all_modes_agree(oracle_lib):
     x = war.burst_frames(1, L, N, zoom, W, 5900)
     rows = {}
     with ZoomFFT(N, zoom, FS, n_win=W) as plan:
+        plan.set_timing(True)
         for average in MODES:
             plan.set_average(average)
             rows[average] = plan.rows(x)
+            assert assert_plan_ran(plan, L, 1).startswith("stockham ")
             _check(rows[average], x, N, zoom, W, average, "short_input")
     for average in ("median", "max"):
         assert_row_close(rows[average][0], rows["mean"][0].astype(np.float64), f"short_input {average} vs mean")
@@ -137,10 +142,12 @@ def test_full_batch_no_split(oracle_lib):
         _, split = _hooks(plan)
         plan.set_timing(True)
         plan.rows(x)
+        assert_plan_ran(plan, L, F)
         assert split(plan._plan) == 1
         for average in ("median", "max"):
             plan.set_average(average)
             rows = plan.rows(x)
+            assert_plan_ran(plan, L, F)
             assert split(plan._plan) == 1
             assert plan.launch_names()[-2:] == ["welch_segs", "welch_select"]
             _check(rows, x, N, zoom, W, average, "full_batch", frames=(0, 1, 767, 1535))
@@ -163,9 +170,11 @@ def test_chunked_scratch_is_bit_identical(N, zoom, W, L, F, welch):
             plan.set_average(average)
             assert cap(plan._plan, 0) == 0
             whole = plan.rows(x)
+            assert " chunk=%d " % F in assert_plan_ran(plan, L, F, welch=welch)
             assert len(plan.launch_names()) == 2
             assert cap(plan._plan, per * 5 // 2) == 0
             chunked = plan.rows(x)
+            assert " chunk=2 " in assert_plan_ran(plan, L, F, welch=welch, cap_bytes=per * 5 // 2)
             assert len(plan.launch_names()) == 2 * ((F + 1) // 2), plan.launch_names()
             assert whole.tobytes() == chunked.tobytes()
         assert cap(plan._plan, -1) == -1
@@ -181,14 +190,18 @@ def test_mean_after_median_is_the_fresh_plan_bytewise():
         a.set_timing(True)
         b.set_timing(True)
         rows_a = a.rows(x)
+        assert_plan_ran(a, L, F)
         names_a = a.launch_names()
         b.set_average("median")
         med1 = b.rows(x)
+        assert_plan_ran(b, L, F)
         med2 = b.rows(x)
+        assert_plan_ran(b, L, F)
         assert med1.tobytes() == med2.tobytes()
         assert not np.array_equal(med1, rows_a)
         b.set_average("mean")
         rows_b = b.rows(x)
+        assert_plan_ran(b, L, F)
         assert rows_b.tobytes() == rows_a.tobytes()
         assert b.launch_names() == names_a
 
@@ -217,7 +230,9 @@ def test_psd_row_average_and_the_cached_mean_plan():
     med = panadapter.psd_row(x, FS, N, zoom, average="median")
     with ZoomFFT(N, zoom, FS, n_win=W, average="median") as plan:
         assert plan.average == "median"
+        plan.set_timing(True)
         np.testing.assert_array_equal(med, plan.rows(x).astype(np.float64))
+        assert_plan_ran(plan, L, 1)
     mean2 = panadapter.psd_row(x, FS, N, zoom)
     assert panadapter._cache(0).plan is mean_plan
     np.testing.assert_array_equal(mean1, mean2)
@@ -233,7 +248,9 @@ def test_ring_process_inherits_the_plan_mode():
     x = war.burst_frame(L, N, 1, W, 6400)
     ring = IQRing(chunk_size=L)
     with ZoomFFT(N, 1, FS, n_win=W, average="max") as plan:
+        plan.set_timing(True)
         want = plan.rows(x)
+        assert_plan_ran(plan, L, 1)
         ring.add(x)
         got = ring.process(plan)
     ring.close()

@@ -15,6 +15,7 @@ import pytest
 import welch_average_ref as war
 import welch_lines_ref as wlr
 from conftest import assert_row_close, row_errors
+from welch_plan_check import assert_plan_ran
 
 pytestmark = pytest.mark.gpu
 FS = war.FS
@@ -108,6 +109,8 @@ def test_lines_vs_float64_reference(oracle_lib, name):
             plan.set_average(average)
             plan.set_segments_per_line(0)
             whole = plan.rows(x)
+            welch = opt.get("welch", 0)
+            assert_plan_ran(plan, L, F, welch=welch)
             assert whole.shape == (F, plan.row_length)
             if opt.get("split") and average == "mean":  # the shape is in the split regime
                 assert split(plan._plan) > 1
@@ -116,6 +119,8 @@ def test_lines_vs_float64_reference(oracle_lib, name):
                 R = wlr.line_count(nseg, g)
                 assert plan.lines(L) == R and R > 1
                 lines = plan.rows(x)
+                desc = assert_plan_ran(plan, L, F, welch=welch)
+                assert (" lines " in desc) == (average == "mean" and 1024 <= N <= 16384 and welch != 2), desc
                 assert lines.shape == (F, R, plan.row_length)
                 if "first" in opt:
                     assert plan.launch_names()[0] == opt["first"], plan.launch_names()
@@ -125,6 +130,7 @@ def test_lines_vs_float64_reference(oracle_lib, name):
                 if average == "mean":  # the other route for mean lines, against the same reference
                     _route(plan, 1)
                     _check(plan.rows(x), x, N, zoom, W, g, average, name + "/scratch")
+                    assert "select=mean_lines" in assert_plan_ran(plan, L, F, welch=welch, lines_route=1)
                     _route(plan, 0)
                     for f in range(F):
                         assert_row_close(_recombined(lines[f], nseg, g), whole[f].astype(np.float64),
@@ -143,9 +149,11 @@ def test_full_batch(oracle_lib, g):
     assert war.nseg_of(L, N, zoom) == 4
     with ZoomFFT(N, zoom, FS, n_win=W, segments_per_line=g) as plan:
         _, split = _hooks(plan)
+        plan.set_timing(True)
         for average in MODES:
             plan.set_average(average)
             lines = plan.rows(x)
+            assert_plan_ran(plan, L, F)
             assert split(plan._plan) == 1
             assert lines.shape == (F, 2, W)
             tiles = lines.reshape(F // 24, 24, 2, W)
@@ -168,17 +176,21 @@ def test_g0_is_unchanged_bytewise():
             a.set_average(average)
             b.set_average(average)
             fresh = a.rows(x)
+            assert_plan_ran(a, L, F)
             names = a.launch_names()
             b.set_segments_per_line(3)
             lines = b.rows(x)
+            assert_plan_ran(b, L, F)
             assert lines.shape == (F, wlr.line_count(nseg, 3), W)
             b.set_segments_per_line(0)
             back = b.rows(x)
+            assert_plan_ran(b, L, F)
             assert back.shape == fresh.shape and back.tobytes() == fresh.tobytes(), average
             assert b.launch_names() == names
             for g in (nseg, nseg + 1, 1000):
                 b.set_segments_per_line(g)
                 one = b.rows(x)
+                assert_plan_ran(b, L, F)
                 assert one.shape == (F, 1, W)
                 assert one.tobytes() == fresh.tobytes(), (average, g)
                 assert b.launch_names() == names
@@ -192,15 +204,18 @@ def test_short_input_branch():
     N, zoom, W, L = 2048, 512, 2048, 319488
     x = war.burst_frames(1, L, N, zoom, W, 7700)[0]
     with ZoomFFT(N, zoom, FS, n_win=W) as plan:
+        plan.set_timing(True)
         for average in MODES:
             plan.set_average(average)
             plan.set_segments_per_line(0)
             row = plan.rows(x)
+            assert_plan_ran(plan, L, 1)
             assert row.shape == (W,)
             for g in (1, 2, 7):
                 plan.set_segments_per_line(g)
                 assert plan.lines(L) == 1
                 lines = plan.rows(x)
+                assert " lines=1 " in assert_plan_ran(plan, L, 1)
                 assert lines.shape == (1, W)
                 assert lines.tobytes() == row.tobytes(), (average, g)
 
@@ -222,10 +237,12 @@ def test_chunked_scratch_is_bit_identical(N, zoom, W, L, F, g, welch):
             plan.set_average(average)
             assert cap(plan._plan, 0) == 0
             whole = plan.rows(x)
+            assert " chunk=%d " % F in assert_plan_ran(plan, L, F, welch=welch, lines_route=1)
             assert len(plan.launch_names()) == 2
             assert plan.rows(x).tobytes() == whole.tobytes()
             assert cap(plan._plan, per * 5 // 2) == 0
             chunked = plan.rows(x)
+            assert " chunk=2 " in assert_plan_ran(plan, L, F, welch=welch, lines_route=1, cap_bytes=per * 5 // 2)
             assert len(plan.launch_names()) == 2 * ((F + 1) // 2), plan.launch_names()
             assert whole.tobytes() == chunked.tobytes(), average
 
@@ -244,6 +261,7 @@ def test_host_batching_offsets_rows_by_lines(oracle_lib):
         for average in MODES:
             plan.set_average(average)
             both = plan.rows(x)
+            assert_plan_ran(plan, L, F // 2)  # (the last of two batches)
             assert "batch_wait" in plan.launch_names()
             halves = np.concatenate([plan.rows(x[:F // 2]), plan.rows(x[F // 2:])])
             assert "batch_wait" not in plan.launch_names()
