@@ -335,6 +335,40 @@ int zfft_line_times(int64_t n_samples, int32_t zoom, int32_t n_fft, double fs, i
 int zfft_ring_process_lines(zfft_ring *ring, zfft_plan *plan, float *rows_out, int32_t max_lines,
                             int32_t *produced);
 
+/* Persistence (digital-phosphor) spectrum: for every column of the plan's rows a histogram of
+ * the levels seen, accumulated on the device from rows the caller pushes -- the model is the
+ * waterfall ring: nothing is hidden inside zfft_process*, and a plan that never enables it
+ * allocates and launches nothing for it.
+ * Binning rule (float32 throughout, reproducible bit for bit in numpy float32):
+ *   lo  = (float)db_min
+ *   inv = (float)(levels / (db_max - db_min))     the division in double, rounded once
+ *   t   = (v - lo) * inv                          each operation rounded to float32, no
+ *                                                 contraction into a fused multiply-add
+ * and v is counted in cell (int)t of its column when t >= 0 and t < levels; any other value is
+ * counted nowhere: NaN, +-inf, the -inf of a zero bin, levels outside the range, db_max itself.
+ * Level 0 is the lowest; the table is hist[level * n_win + j], column j as in a row; columns at
+ * or beyond zfft_plan_row_length stay 0.  rows_seen grows by `count` with every push, whatever
+ * its values.  Counts are uint32 and wrap modulo 2^32 when a cell sees more than 2^32 - 1
+ * values between decays or resets: zfft_persistence_decay is the remedy.
+ * Every zfft_persistence_* call on a plan with persistence off returns ZFFT_EINVAL
+ * (zfft_persistence_shape after reporting 0 levels).  With zfft_plan_timing on, a push reports
+ * its kernel as "persist_hist" (zfft_plan_timings then describes the push, the last timed call). */
+/* levels = 0 (default): off, frees the table.  levels in [2, 256], db_min < db_max finite:
+ * allocates and zeroes a table of levels x n_win uint32 counts (level-major, column j as in a
+ * row) and a row counter.  Anything else ZFFT_EINVAL.  Re-enabling with new parameters resets. */
+int zfft_plan_persistence(zfft_plan *plan, int32_t levels, double db_min, double db_max);
+int zfft_persistence_shape(const zfft_plan *plan, int32_t *levels, int32_t *cols);
+/* Bin `count` rows of n_win floats (row stride n_win; only the first zfft_plan_row_length
+ * columns of each row are read).  Enqueued on hip_stream, no sync; ordered after earlier
+ * work on that stream (as zfft_waterfall_push_device). */
+int zfft_persistence_push_device(zfft_plan *plan, const float *d_rows, int32_t count, void *hip_stream);
+int zfft_persistence_push(zfft_plan *plan, const float *rows /* host */, int32_t count);  /* synchronous */
+/* every count c -> floor(c * keep) and rows_seen likewise, in double; 0 <= keep <= 1 */
+int zfft_persistence_decay(zfft_plan *plan, double keep);
+int zfft_persistence_reset(zfft_plan *plan);
+/* waits for the plan's enqueued pushes; hist_out levels*n_win uint32; rows_seen may be NULL */
+int zfft_persistence_read(zfft_plan *plan, uint32_t *hist_out, uint64_t *rows_seen);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

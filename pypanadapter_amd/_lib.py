@@ -67,6 +67,8 @@ EXPORTS = [
     "zfft_host_alloc", "zfft_host_free",
     "zfft_device_count", "zfft_version",
     "zfft_plan_segments_per_line", "zfft_line_count", "zfft_line_times", "zfft_ring_process_lines",
+    "zfft_plan_persistence", "zfft_persistence_shape", "zfft_persistence_push_device",
+    "zfft_persistence_push", "zfft_persistence_decay", "zfft_persistence_reset", "zfft_persistence_read",
 ]
 
 _lib = None
@@ -145,6 +147,13 @@ def load(path: str = ""):
         "zfft_line_count": (I64, [I64, I32, I32, I32]),
         "zfft_line_times": (ctypes.c_int, [I64, I32, I32, D, I32, P, I32, ctypes.POINTER(I32)]),
         "zfft_ring_process_lines": (ctypes.c_int, [P, P, P, I32, ctypes.POINTER(I32)]),
+        "zfft_plan_persistence": (ctypes.c_int, [P, I32, D, D]),
+        "zfft_persistence_shape": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+        "zfft_persistence_push_device": (ctypes.c_int, [P, P, I32, P]),
+        "zfft_persistence_push": (ctypes.c_int, [P, P, I32]),
+        "zfft_persistence_decay": (ctypes.c_int, [P, D]),
+        "zfft_persistence_reset": (ctypes.c_int, [P]),
+        "zfft_persistence_read": (ctypes.c_int, [P, P, ctypes.POINTER(ctypes.c_uint64)]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

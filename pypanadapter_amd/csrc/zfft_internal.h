@@ -1,5 +1,5 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
-// zfft_waterfall.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
+// zfft_waterfall.cpp, zfft_persist.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
 // (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
@@ -383,6 +383,20 @@ hipError_t launch_waterfall_render(const float *ring, int H, int W, int64_t off,
 hipError_t launch_autolevel_hist_hi(const float *ring, int64_t n, unsigned *hist, hipStream_t st);
 hipError_t launch_autolevel_hist_lo(const float *ring, int64_t n, const unsigned *bins, int nbins,
                                     unsigned *hist, hipStream_t st);
+// Persistence spectrum (zfft.h's binning rule): hist[level * n_win + j] += the number of rows
+// r < count whose value rows[r * row_stride + j], j < row_len, falls in `level`.  One launch:
+// a workgroup owns 64 consecutive columns and one of `slices` row slices (persist_slices),
+// counts in LDS and adds its non-zero cells to hist at the end.
+struct PersistGeom {
+  int n_win, row_len, levels;
+  float lo, inv;
+  int slices = 0, slice_rows = 0;  // (set by the launch)
+};
+int persist_slices(int count, int row_len);
+hipError_t launch_persist_hist(const float *rows, int64_t row_stride, int count, PersistGeom g,
+                               unsigned *hist, hipStream_t st);
+// hist[i] = floor((double)hist[i] * keep), i < n
+hipError_t launch_persist_decay(unsigned *hist, int64_t n, double keep, hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

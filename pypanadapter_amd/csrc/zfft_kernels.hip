@@ -1973,4 +1973,119 @@ hipError_t launch_autolevel_hist_lo(const float *ring, int64_t n, const unsigned
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ persistence spectrum
+// hist[level][column] += rows whose value falls in that level (zfft.h's binning rule; DESIGN
+// §3.3.3).  A workgroup owns kPersistCols = 64 consecutive columns and one slice of the rows:
+// lane l of every wave is column 64 blockIdx.x + l, so a row is one coalesced 256-B load per
+// wave and a count goes to h[level * 64 + l] -- the lane alone decides the bank, so an update
+// never conflicts inside a wave, however concentrated the column's levels are.  The counts stay
+// in LDS (levels x 64 uint32: 64 KB at 256 levels, two workgroups per CU) until the slice is
+// done; then the non-zero cells go to the table with one vector atomicAdd each -- integer sums,
+// so the table does not depend on the order.  With two workgroups per CU the loads must be
+// deep: a wave loads kPersistU = 16 rows at once and the next 16 before it counts these, so a
+// workgroup of 8 waves keeps up to 256 rows (64 KB) in flight.  The waves share the columns'
+// counters (rows interleaved in runs of 16), so the update is an LDS atomic (ds_add_u32, no
+// return); ZFFT_PERSIST_WAVES = 1 builds the other form, one wave owning its columns with a
+// plain read-modify-write, for the A/B of DESIGN §3.3.3.  Columns >= row_len (a width that is no
+// multiple of 64, the one-sided crop) are masked lanes.
+#ifndef ZFFT_PERSIST_WAVES
+#define ZFFT_PERSIST_WAVES 8  // measured against 1, 2, 4 and 16: DESIGN §3.3.3
+#endif
+constexpr int kPersistCols = 64, kPersistWaves = ZFFT_PERSIST_WAVES, kPersistU = 16;
+constexpr int kPersistBatch = kPersistU * kPersistWaves;  // rows a workgroup loads at once
+constexpr int kPersistGrid = 512;                         // workgroups of a large push: two per CU
+static_assert(kPersistWaves == 1 || kPersistWaves == 2 || kPersistWaves == 4 || kPersistWaves == 8 ||
+                  kPersistWaves == 16,
+              "waves per persistence workgroup");
+
+template <int WAVES>
+__device__ __forceinline__ void persist_count(unsigned *h, int lane, float v, float lo, float inv, float flev) {
+  const float t = __fmul_rn(__fsub_rn(v, lo), inv);  // two roundings, never an fma
+  if (t >= 0.f && t < flev) {                        // NaN fails both
+    unsigned *c = h + (int)t * kPersistCols + lane;
+    if constexpr (WAVES == 1)
+      *c += 1u;
+    else
+      atomicAdd(c, 1u);
+  }
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void persist_hist_kernel(const float *__restrict__ rows,
+                                                                   int64_t row_stride, int count,
+                                                                   PersistGeom g, unsigned *__restrict__ hist) {
+  extern __shared__ unsigned persist_h[];  // [levels][64]
+  constexpr int NT = 64 * WAVES, U = kPersistU;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = blockIdx.x * kPersistCols + lane;
+  const int cells = g.levels * kPersistCols;
+  for (int i = threadIdx.x; i < cells; i += NT) persist_h[i] = 0u;
+  __syncthreads();
+  const int r0 = blockIdx.y * g.slice_rows, r1 = min(count, r0 + g.slice_rows);
+  if (col < g.row_len && r0 < r1) {
+    const float *p = rows + col;
+    const float flev = (float)g.levels;
+    // rows past the slice's end are loaded as its last row (in bounds) and not counted
+    auto load = [&](int r, float (&v)[U]) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = p[(int64_t)min(r + u, r1 - 1) * row_stride];
+    };
+    int r = r0 + wave * U;
+    float v[U], nx[U];
+    load(r, v);
+    for (; r < r1; r += kPersistBatch) {
+      const bool more = r + kPersistBatch < r1;
+      if (more) load(r + kPersistBatch, nx);  // the next batch in flight behind this one's counts
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (r + u < r1) persist_count<WAVES>(persist_h, lane, v[u], g.lo, g.inv, flev);
+      if (more) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = nx[u];
+      }
+    }
+  }
+  __syncthreads();
+  // cell i = level * 64 + column-in-block: non-zero only in columns < row_len <= n_win
+  for (int i = threadIdx.x; i < cells; i += NT) {
+    const unsigned c = persist_h[i];
+    if (c) atomicAdd(hist + (int64_t)(i >> 6) * g.n_win + blockIdx.x * kPersistCols + (i & 63), c);
+  }
+}
+
+__global__ __launch_bounds__(256) void persist_decay_kernel(unsigned *__restrict__ hist, int64_t n, double keep) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) hist[i] = (unsigned)floor((double)hist[i] * keep);
+}
+
+// Row slices of a push: about 256 rows each while that gives at most kPersistGrid workgroups,
+// longer beyond.  512 workgroups are one resident round at 256 levels (64 KB of counters: two
+// per CU), and the time of a large push follows the rounds, not the rows -- cfg2's 69,632 x 512
+// takes 0.100 ms as 2048 workgroups of 272 rows and 0.040 ms as 512 of 1088 (8 column blocks x
+// 64 slices).  Up to 256 rows are one slice, a single row a launch of ceil(row_len / 64) small
+// workgroups.
+int persist_slices(int count, int row_len) {
+  const int cb = (row_len + kPersistCols - 1) / kPersistCols;
+  const int by_rows = (count + 255) / 256, by_grid = std::max(1, kPersistGrid / std::max(cb, 1));
+  return std::max(1, std::min(by_rows, by_grid));
+}
+
+hipError_t launch_persist_hist(const float *rows, int64_t row_stride, int count, PersistGeom g,
+                               unsigned *hist, hipStream_t st) {
+  if (count < 1 || g.row_len < 1 || g.row_len > g.n_win || g.levels < 2 || g.levels > 256)
+    return hipErrorInvalidValue;
+  g.slices = persist_slices(count, g.row_len);
+  g.slice_rows = (count + g.slices - 1) / g.slices;
+  const dim3 grid((unsigned)((g.row_len + kPersistCols - 1) / kPersistCols), (unsigned)g.slices);
+  const size_t lds = (size_t)g.levels * kPersistCols * sizeof(unsigned);  // <= 64 KB
+  hipLaunchKernelGGL(persist_hist_kernel<kPersistWaves>, grid, dim3(64 * kPersistWaves), lds, st, rows,
+                     row_stride, count, g, hist);
+  return hipGetLastError();
+}
+
+hipError_t launch_persist_decay(unsigned *hist, int64_t n, double keep, hipStream_t st) {
+  hipLaunchKernelGGL(persist_decay_kernel, dim3(nblocks(n, 256)), dim3(256), 0, st, hist, n, keep);
+  return hipGetLastError();
+}
+
 }  // namespace zfft

@@ -1,5 +1,6 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
-// (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp).  Not part of the C-ABI.
+// (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp).  Not part
+// of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,6 +107,14 @@ struct zfft_plan {
   DevBuf img64;                    // float64 image of the display entries
   float *row_pin = nullptr;        // page-locked staging of host rows the display kernels read
   size_t row_pin_cap = 0;          //   in place (no H2D copy command); bytes
+  // persistence spectrum (zfft_plan_persistence; zfft_persist.cpp): ps_levels x n_win uint32
+  // counts, level-major; 0 levels = off (no buffer).  ps_lo / ps_inv are the binning rule's
+  // float32 constants; ps_rows the rows pushed (host side: pushes and decays are in call order)
+  int ps_levels = 0;
+  float ps_lo = 0.f, ps_inv = 0.f;
+  uint64_t ps_rows = 0;
+  int ps_slices = 0;               // row slices of the last push (test hook zfft__plan_persist_slices)
+  DevBuf ps_hist, ps_stage;        // the table; device staging of zfft_persistence_push's host rows
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the

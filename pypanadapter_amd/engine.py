@@ -394,6 +394,65 @@ class ZoomFFT:
                                                     ctypes.c_void_p(stream or None)),
               "zfft_waterfall_render_device")
 
+    # ---------------------------------------------------------------- persistence spectrum
+    def set_persistence(self, levels: int, db_min: float = 0.0, db_max: float = 0.0) -> None:
+        """The persistence (digital-phosphor) table (zfft_plan_persistence): per column a
+        histogram of the pushed rows' levels, `levels` (2..256) equal steps from db_min (level 0)
+        up to, not including, db_max; values outside, NaN and infinities are counted nowhere.
+        Zeroes the table; levels = 0 turns it off and frees it.  The binning rule is in
+        include/zfft.h, bit for bit reproducible in numpy float32."""
+        check(self.lib.zfft_plan_persistence(self._plan, int(levels), float(db_min), float(db_max)),
+              "zfft_plan_persistence")
+
+    def persistence_shape(self):
+        lv, w = ctypes.c_int32(), ctypes.c_int32()
+        check(self.lib.zfft_persistence_shape(self._plan, ctypes.byref(lv), ctypes.byref(w)),
+              "zfft_persistence_shape")
+        return lv.value, w.value
+
+    def persistence_push(self, rows) -> None:
+        """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row),
+        binned into the table; synchronous."""
+        r = np.asarray(rows, dtype=np.float32)
+        r = r.reshape(-1, r.shape[-1])
+        if r.shape[1] != self.n_win:
+            if r.shape[1] != self.row_length:
+                raise ValueError("rows must be n_win or row_length wide")
+            full = np.full((r.shape[0], self.n_win), np.nan, dtype=np.float32)  # the tail is never read
+            full[:, :r.shape[1]] = r
+            r = full
+        r = np.ascontiguousarray(r)
+        check(self.lib.zfft_persistence_push(self._plan, r.ctypes.data_as(ctypes.c_void_p), r.shape[0]),
+              "zfft_persistence_push")
+
+    def persistence_push_device(self, d_rows_ptr: int, count: int, stream: int = 0) -> None:
+        """`count` device rows of n_win floats (e.g. what process_device wrote), enqueued on
+        `stream`, no sync."""
+        check(self.lib.zfft_persistence_push_device(self._plan, ctypes.c_void_p(d_rows_ptr), int(count),
+                                                    ctypes.c_void_p(stream or None)),
+              "zfft_persistence_push_device")
+
+    def persistence_decay(self, keep: float) -> None:
+        """Every count c becomes floor(c * keep), rows_seen likewise; 0 <= keep <= 1."""
+        check(self.lib.zfft_persistence_decay(self._plan, float(keep)), "zfft_persistence_decay")
+
+    def persistence_reset(self) -> None:
+        check(self.lib.zfft_persistence_reset(self._plan), "zfft_persistence_reset")
+
+    def persistence(self):
+        """(hist, rows_seen): uint32 counts of shape (levels, n_win), level 0 the lowest, and the
+        number of rows pushed since the last reset (scaled by the decays)."""
+        hist = np.empty(self.persistence_shape(), dtype=np.uint32)
+        seen = ctypes.c_uint64()
+        check(self.lib.zfft_persistence_read(self._plan, hist.ctypes.data_as(ctypes.c_void_p),
+                                             ctypes.byref(seen)), "zfft_persistence_read")
+        return hist, int(seen.value)
+
+    def persistence_density(self) -> np.ndarray:
+        """float64 hist / max(rows_seen, 1): the share of the rows a column spent in each level."""
+        hist, seen = self.persistence()
+        return hist / float(max(seen, 1))
+
 
 _IN_DTYPES = {"complex64": (0, np.complex64, 1), "complex32": (1, np.float16, 2),
               "cu8": (2, np.uint8, 2), "f32": (3, np.float32, 1)}

@@ -258,6 +258,72 @@ class Waterfall:
         return self._need_plan().waterfall_push_emit(self._take_pending(), False, out)
 
 
+class Persistence:
+    """The persistence (digital-phosphor) view of a stream of rows: per column a histogram of the
+    levels seen, on the device (ZoomFFT.set_persistence; binning rule in include/zfft.h).
+
+        view = Persistence(levels=200, db_min=-220.0, db_max=-20.0)
+        view.update(psd_lines(chunk, fs, N, zoom, 1))
+        img = view.image()          # uint32 (levels, W), level 0 = db_min, for an ImageItem
+
+    `update` takes one row or (R, W) rows and lazily builds a plan for their width, like
+    `Waterfall`; a new width rebuilds it and starts from zeros.  `decay(keep)` fades the counts
+    (c -> floor(c keep)), `reset()` clears them, `density()` is image / rows seen."""
+
+    def __init__(self, levels: int = 200, db_min: float = -220.0, db_max: float = -20.0,
+                 device: int = 0, fs: float = 2.4e6):
+        self.levels, self.db_min, self.db_max = int(levels), float(db_min), float(db_max)
+        self.device = device
+        self.fs = fs
+        self.width = 0
+        self._plan: ZoomFFT | None = None
+
+    def _ensure(self, width: int):
+        if width != self.width or self._plan is None:
+            self.close()
+            n_win = width + (width & 1)  # a plan's rows are even: an odd width gets a NaN column
+            n_fft = 1 << max(5, (n_win - 1).bit_length())
+            self._plan = ZoomFFT(n_fft, 1, self.fs, n_win=n_win, device=self.device)
+            self._plan.set_persistence(self.levels, self.db_min, self.db_max)
+            self.width = width
+
+    def _need_plan(self):
+        if self._plan is None:
+            raise AttributeError("the persistence image is created by the first update")
+        return self._plan
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+            self.width = 0
+
+    def update(self, psd_rows) -> None:
+        rows = np.asarray(psd_rows, dtype=np.float32)
+        rows = rows.reshape(-1, rows.shape[-1])
+        width = rows.shape[1]
+        self._ensure(width)
+        if self._plan.n_win != width:
+            rows = np.concatenate([rows, np.full((len(rows), 1), np.nan, np.float32)], axis=1)
+        self._plan.persistence_push(rows)
+
+    def image(self) -> np.ndarray:
+        return self._need_plan().persistence()[0][:, :self.width]
+
+    @property
+    def rows_seen(self) -> int:
+        return self._need_plan().persistence()[1]
+
+    def density(self) -> np.ndarray:
+        return self._need_plan().persistence_density()[:, :self.width]
+
+    def decay(self, keep: float) -> None:
+        self._need_plan().persistence_decay(keep)
+
+    def reset(self) -> None:
+        self._need_plan().persistence_reset()
+
+
 class Data:
     """pypanadapter_thread.py's `Data` (T:1400-1483) on the pinned double-buffered IQRing
     (SURVEY §8f-1), same calls: the reader thread's `add(chunk)` (T:2191) and the PSD
