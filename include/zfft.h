@@ -369,6 +369,58 @@ int zfft_persistence_reset(zfft_plan *plan);
 /* waits for the plan's enqueued pushes; hist_out levels*n_win uint32; rows_seen may be NULL */
 int zfft_persistence_read(zfft_plan *plan, uint32_t *hist_out, uint64_t *rows_seen);
 
+/* Signal detection on rows: per row a noise floor, the emissions above floor + threshold, and
+ * per column a count of how often it was part of one -- from rows the caller holds on the
+ * device, in the model of the ring and of persistence: nothing is hidden inside zfft_process*,
+ * and a plan that never enables it allocates and launches nothing for it.
+ * A row is the first n = zfft_plan_row_length(plan) floats of a stride of n_win.  Every value
+ * here is in row units, and rows are 20*log10(PSD): a POWER ratio of 4 is 12.04 units, not
+ * 6.02 -- threshold_db is a difference of row values, nothing else.
+ * The rule (float32 values, reproducible bit for bit in numpy float32):
+ *   1. population: the finite values of the row; NaN, +inf and -inf are left out.  m = their
+ *      number.  m == 0: floor = NaN and the row has no emissions.
+ *   2. floor: the value of 0-based rank k = (int64)floor(q * (double)(m - 1)) among the finite
+ *      values in ascending order, q the plan's quantile in [0, 1] (q = 0.5: the lower median).
+ *      No interpolation: the floor is one of the row's own values, bit for bit (-0.0 and 0.0
+ *      compare equal; which of the two a zero floor is, is not defined).  numpy:
+ *      np.sort(finite)[k].
+ *   3. thr = floor + (float)threshold_db, one float32 addition; threshold_db any finite double.
+ *      Column j is on when v[j] >= thr: +inf is on, NaN and -inf are off.
+ *   4. an emission is a maximal run [first, last] of consecutive on columns with
+ *      last - first + 1 >= min_width (min_width >= 1).  Gaps are not bridged.
+ *   5. its record: first, last, peak = the lowest column of the run that holds the run's
+ *      maximum, peak_db = that value, unchanged.
+ *   6. per row i: floor[i]; found[i] = the number of kept runs, those beyond the cap included;
+ *      events[i * K + 0 .. K - 1] = the first min(found, K) runs in ascending column order, the
+ *      remaining slots all-zero records (K = max_per_row in [1, 32]): the outputs are fully
+ *      defined and need no clearing by the caller.
+ *   7. occupancy: occ[j], a uint32 per column (n_win in all), grows by 1 for every column of
+ *      every kept run, recorded within K or not; columns at or beyond n stay 0.  rows_seen grows
+ *      by `count` with every call.  Counts wrap modulo 2^32.
+ * Every zfft_detect* call on a plan with detection off returns ZFFT_EINVAL (zfft_detect_shape
+ * after reporting max_per_row 0).  With zfft_plan_timing on, a call reports its kernel as
+ * "detect_rows" (zfft_plan_timings then describes that call, the last timed one). */
+typedef struct zfft_emission {
+  int32_t first, last, peak;
+  float peak_db;
+} zfft_emission; /* 16 bytes */
+/* max_per_row = 0 (default): off, frees the occupancy table.  Otherwise max_per_row in [1, 32],
+ * quantile in [0, 1], threshold_db finite, min_width in [1, n_win]; anything else ZFFT_EINVAL.
+ * Re-enabling resets the occupancy. */
+int zfft_plan_detect(zfft_plan *plan, double quantile, double threshold_db, int32_t min_width, int32_t max_per_row);
+int zfft_detect_shape(const zfft_plan *plan, int32_t *max_per_row, int32_t *cols);
+/* count rows of stride n_win on the device; outputs on the device: count floats, count int32,
+ * count * max_per_row records (16-byte aligned).  Enqueued on hip_stream, no sync; ordered after
+ * earlier work on that stream (as zfft_persistence_push_device). */
+int zfft_detect_device(zfft_plan *plan, const float *d_rows, int32_t count, float *d_floor, int32_t *d_found,
+                       zfft_emission *d_events, void *hip_stream);
+/* host rows and host outputs, synchronous */
+int zfft_detect(zfft_plan *plan, const float *rows, int32_t count, float *floor_out, int32_t *found_out,
+                zfft_emission *events_out);
+/* waits for the plan's enqueued calls; occ_out n_win uint32; rows_seen may be NULL */
+int zfft_detect_occupancy(zfft_plan *plan, uint32_t *occ_out, uint64_t *rows_seen);
+int zfft_detect_reset(zfft_plan *plan); /* zeroes occupancy and rows_seen */
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

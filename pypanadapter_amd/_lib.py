@@ -69,6 +69,8 @@ EXPORTS = [
     "zfft_plan_segments_per_line", "zfft_line_count", "zfft_line_times", "zfft_ring_process_lines",
     "zfft_plan_persistence", "zfft_persistence_shape", "zfft_persistence_push_device",
     "zfft_persistence_push", "zfft_persistence_decay", "zfft_persistence_reset", "zfft_persistence_read",
+    "zfft_plan_detect", "zfft_detect_shape", "zfft_detect_device", "zfft_detect", "zfft_detect_occupancy",
+    "zfft_detect_reset",
 ]
 
 _lib = None
@@ -154,6 +156,12 @@ def load(path: str = ""):
         "zfft_persistence_decay": (ctypes.c_int, [P, D]),
         "zfft_persistence_reset": (ctypes.c_int, [P]),
         "zfft_persistence_read": (ctypes.c_int, [P, P, ctypes.POINTER(ctypes.c_uint64)]),
+        "zfft_plan_detect": (ctypes.c_int, [P, D, D, I32, I32]),
+        "zfft_detect_shape": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+        "zfft_detect_device": (ctypes.c_int, [P, P, I32, P, P, P, P]),
+        "zfft_detect": (ctypes.c_int, [P, P, I32, P, P, P]),
+        "zfft_detect_occupancy": (ctypes.c_int, [P, P, ctypes.POINTER(ctypes.c_uint64)]),
+        "zfft_detect_reset": (ctypes.c_int, [P]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

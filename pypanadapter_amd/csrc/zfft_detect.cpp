@@ -1,0 +1,166 @@
+// zfft_detect.cpp -- the row detector of libzfft.so: per row a noise floor, the emissions above
+// floor + threshold and a per-column occupancy count, from rows the caller holds on the device
+// (C-ABI and rule: zfft.h; kernel: detect_kernels.hip; form chooser: zfft_detect_plan.h;
+// DESIGN §3.3.4).  The model is zfft_persist.cpp's: nothing runs inside zfft_process*.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "zfft.h"
+#include "zfft_plan.h"
+
+using namespace zfft;
+
+namespace {
+
+constexpr int32_t kMaxCount = 1 << 26;  // rows per call (count * max_per_row records stay below 2^31)
+
+int need_on(const zfft_plan *p) {
+  return p->dt_k ? ZFFT_OK : fail(ZFFT_EINVAL, "detection is off (zfft_plan_detect)");
+}
+
+int zero_occupancy(zfft_plan *p) {
+  int rc = use_stream(p, p->stream);
+  if (rc) return rc;
+  hipError_t e = hipMemsetAsync(p->dt_occ.p, 0, (size_t)p->cfg.n_win * sizeof(unsigned), p->stream);
+  if (e != hipSuccess) return hip_fail(e, "detect reset");
+  p->dt_rows = 0;
+  return done_on(p, p->stream);
+}
+
+}  // namespace
+
+// Test hook (not part of include/zfft.h): the form a call on `count` rows of this plan takes.
+extern "C" int zfft__plan_detect_form(const zfft_plan *p, int32_t count, int32_t *waves, int32_t *per,
+                                      int32_t *grid) {
+  if (!p || !waves || !per || !grid) return ZFFT_EINVAL;
+  const DetectForm f = choose_detect(row_length(p), count);
+  if (!f.ok()) return ZFFT_EINVAL;
+  *waves = f.waves;
+  *per = f.per;
+  *grid = f.grid;
+  return ZFFT_OK;
+}
+
+extern "C" {
+
+int zfft_plan_detect(zfft_plan *p, double quantile, double threshold_db, int32_t min_width,
+                     int32_t max_per_row) {
+  int rc = enter(p);
+  if (rc) return rc;
+  if (max_per_row == 0) {
+    rc = quiesce(p);  // an enqueued call may still add to the table and read the staging
+    if (rc) return rc;
+    p->dt_occ.release();
+    p->dt_stage.release();
+    p->dt_out.release();
+    p->dt_k = 0;
+    p->dt_rows = 0;
+    return ZFFT_OK;
+  }
+  if (max_per_row < 1 || max_per_row > kDetectMaxPerRow || !(quantile >= 0.0 && quantile <= 1.0) ||
+      !std::isfinite(threshold_db) || min_width < 1 || min_width > p->cfg.n_win)
+    return fail(ZFFT_EINVAL, "detect: max_per_row 0 (off) or in [1, 32], quantile in [0, 1], threshold_db "
+                             "finite, min_width in [1, n_win]");
+  if (p->dt_occ.ensure((size_t)p->cfg.n_win * sizeof(unsigned)) != hipSuccess) {  // (n_win is the plan's: never grows)
+    p->dt_k = 0;
+    return fail(ZFFT_ENOMEM, "detect occupancy allocation failed");
+  }
+  p->dt_k = max_per_row;
+  p->dt_q = quantile;
+  p->dt_thr = (float)threshold_db;
+  p->dt_min_width = min_width;
+  return zero_occupancy(p);
+}
+
+int zfft_detect_shape(const zfft_plan *p, int32_t *max_per_row, int32_t *cols) {
+  if (!p || !max_per_row || !cols) return fail(ZFFT_EINVAL, "null argument");
+  *max_per_row = p->dt_k;
+  *cols = p->cfg.n_win;
+  return need_on(p);
+}
+
+int zfft_detect_device(zfft_plan *p, const float *d_rows, int32_t count, float *d_floor, int32_t *d_found,
+                       zfft_emission *d_events, void *hip_stream) {
+  int rc = enter(p);
+  if (rc) return rc;
+  rc = need_on(p);
+  if (rc) return rc;
+  if (!d_rows || !d_floor || !d_found || !d_events || count < 1 || count > kMaxCount)
+    return fail(ZFFT_EINVAL, "bad rows / outputs / count");
+  if ((uintptr_t)d_events & 15) return fail(ZFFT_EINVAL, "detect: the records must be 16-byte aligned");
+  const DetectGeom g{p->cfg.n_win, row_length(p), p->dt_q, p->dt_thr, p->dt_min_width, p->dt_k};
+  const DetectForm f = choose_detect(g.row_len, count);
+  if (!f.ok()) return fail(ZFFT_EINVAL, "detect: the plan's rows are empty");
+  hipStream_t st = pick_stream(p, hip_stream);
+  rc = use_stream(p, st);  // after the table's zeroing and earlier calls, on any stream
+  if (rc) return rc;
+  p->dt_rows += (uint64_t)count;
+  p->n_marks = 0;
+  mark(p, st, "start");
+  hipError_t e = launch_detect_rows(d_rows, p->cfg.n_win, count, g, f, d_floor, d_found, d_events,
+                                    p->dt_occ.as<unsigned>(), st);
+  if (e != hipSuccess) return hip_fail(e, "detect");
+  mark(p, st, "detect_rows");
+  return done_on(p, st);
+}
+
+int zfft_detect(zfft_plan *p, const float *rows, int32_t count, float *floor_out, int32_t *found_out,
+                zfft_emission *events_out) {
+  int rc = enter(p);
+  if (rc) return rc;
+  rc = need_on(p);
+  if (rc) return rc;
+  if (!rows || !floor_out || !found_out || !events_out || count < 1 || count > kMaxCount)
+    return fail(ZFFT_EINVAL, "bad rows / outputs / count");
+  const size_t in_bytes = (size_t)count * p->cfg.n_win * sizeof(float);
+  // the records first (16-byte aligned), then the floors, then the counts
+  const size_t ev_bytes = (size_t)count * p->dt_k * sizeof(zfft_emission), n4 = (size_t)count * 4;
+  if (p->dt_stage.cap < in_bytes || p->dt_out.cap < ev_bytes + 2 * n4) {
+    rc = quiesce(p);  // growing frees what an earlier call may still use
+    if (rc) return rc;
+    if (p->dt_stage.ensure(in_bytes) != hipSuccess || p->dt_out.ensure(ev_bytes + 2 * n4) != hipSuccess)
+      return fail(ZFFT_ENOMEM, "detect staging allocation failed");
+  }
+  rc = use_stream(p, p->stream);  // the staging may still be read by the previous call
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(p->dt_stage.p, rows, in_bytes, hipMemcpyHostToDevice, p->stream);
+  if (e != hipSuccess) return hip_fail(e, "H2D rows");
+  char *out = p->dt_out.as<char>();
+  rc = zfft_detect_device(p, p->dt_stage.as<float>(), count, (float *)(out + ev_bytes),
+                          (int32_t *)(out + ev_bytes + n4), (zfft_emission *)out, p->stream);
+  if (rc) return rc;
+  e = hipMemcpyAsync(events_out, out, ev_bytes, hipMemcpyDeviceToHost, p->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(floor_out, out + ev_bytes, n4, hipMemcpyDeviceToHost, p->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(found_out, out + ev_bytes + n4, n4, hipMemcpyDeviceToHost, p->stream);
+  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+  return e == hipSuccess ? ZFFT_OK : hip_fail(e, "detect D2H");
+}
+
+int zfft_detect_occupancy(zfft_plan *p, uint32_t *occ_out, uint64_t *rows_seen) {
+  int rc = enter(p);
+  if (rc) return rc;
+  rc = need_on(p);
+  if (rc) return rc;
+  if (!occ_out) return fail(ZFFT_EINVAL, "null output");
+  rc = use_stream(p, p->stream);
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(occ_out, p->dt_occ.p, (size_t)p->cfg.n_win * sizeof(unsigned),
+                                hipMemcpyDeviceToHost, p->stream);
+  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+  if (e != hipSuccess) return hip_fail(e, "detect occupancy read");
+  if (rows_seen) *rows_seen = p->dt_rows;
+  return ZFFT_OK;
+}
+
+int zfft_detect_reset(zfft_plan *p) {
+  int rc = enter(p);
+  if (rc) return rc;
+  rc = need_on(p);
+  if (rc) return rc;
+  return zero_occupancy(p);
+}
+
+}  // extern "C"

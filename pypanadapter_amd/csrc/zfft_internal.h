@@ -1,6 +1,7 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
-// zfft_waterfall.cpp, zfft_persist.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
-// (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip).  Not part of the C-ABI.
+// zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and
+// the HIP kernels (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, detect_kernels.hip).  Not part
+// of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,7 +10,10 @@
 #include <string>
 #include <vector>
 
+#include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
 #include "zfft_welch_plan.h"  // the Welch forms' domains (kMaxLdsFft, kDifMin / kDifMax, ...), WelchSel
+
+struct zfft_emission;  // zfft.h
 
 namespace zfft {
 
@@ -397,6 +401,19 @@ hipError_t launch_persist_hist(const float *rows, int64_t row_stride, int count,
                                unsigned *hist, hipStream_t st);
 // hist[i] = floor((double)hist[i] * keep), i < n
 hipError_t launch_persist_decay(unsigned *hist, int64_t n, double keep, hipStream_t st);
+// Row detector (zfft.h's rule; detect_kernels.hip): per row r < count of rows[r * row_stride + j],
+// j < row_len, the floor, the number of kept runs and the first max_per_row records, and occ[j]
+// += 1 for every column of a kept run.  `form` is choose_detect's (refused where it does not
+// hold row_len); events 16-byte aligned.
+struct DetectGeom {
+  int n_win, row_len;
+  double q;        // the floor's quantile
+  float thr_add;   // (float)threshold_db
+  int min_width, max_per_row;
+};
+hipError_t launch_detect_rows(const float *rows, int64_t row_stride, int count, const DetectGeom &g,
+                              const DetectForm &form, float *floor_out, int32_t *found_out,
+                              zfft_emission *events, unsigned *occ, hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

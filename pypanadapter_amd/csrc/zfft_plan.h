@@ -1,6 +1,6 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
-// (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp).  Not part
-// of the C-ABI.
+// (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
+// zfft_detect.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -115,6 +115,14 @@ struct zfft_plan {
   uint64_t ps_rows = 0;
   int ps_slices = 0;               // row slices of the last push (test hook zfft__plan_persist_slices)
   DevBuf ps_hist, ps_stage;        // the table; device staging of zfft_persistence_push's host rows
+  // row detector (zfft_plan_detect; zfft_detect.cpp): dt_k = max_per_row, 0 = off (no buffer).
+  // dt_occ holds n_win uint32 counts, dt_rows the rows seen (host side, in call order); dt_stage
+  // and dt_out are the device staging of zfft_detect's host rows and outputs
+  int dt_k = 0, dt_min_width = 1;
+  double dt_q = 0.5;
+  float dt_thr = 0.f;
+  uint64_t dt_rows = 0;
+  DevBuf dt_occ, dt_stage, dt_out;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the

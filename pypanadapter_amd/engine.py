@@ -453,6 +453,73 @@ class ZoomFFT:
         hist, seen = self.persistence()
         return hist / float(max(seen, 1))
 
+    # ---------------------------------------------------------------- signal detection on rows
+    def set_detect(self, quantile: float = 0.5, threshold_db: float = 12.0, min_width: int = 1,
+                   max_per_row: int = 8) -> None:
+        """The row detector (zfft_plan_detect): per row the noise floor (the value of rank
+        floor(quantile (m - 1)) among its m finite values), the emissions (runs of at least
+        `min_width` columns at or above floor + threshold_db, at most `max_per_row` (1..32)
+        recorded per row) and a per-column occupancy count.  threshold_db is in row units,
+        20 log10(PSD): a power ratio of 4 is 12.04.  Zeroes the occupancy; max_per_row = 0
+        turns detection off.  The rule is in include/zfft.h, bit for bit reproducible in numpy."""
+        check(self.lib.zfft_plan_detect(self._plan, float(quantile), float(threshold_db), int(min_width),
+                                        int(max_per_row)), "zfft_plan_detect")
+
+    def detect_shape(self):
+        """(max_per_row, n_win)."""
+        k, w = ctypes.c_int32(), ctypes.c_int32()
+        check(self.lib.zfft_detect_shape(self._plan, ctypes.byref(k), ctypes.byref(w)), "zfft_detect_shape")
+        return k.value, w.value
+
+    def detect(self, rows):
+        """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row):
+        (floor float32[count], found int32[count], events), events a structured array of shape
+        (count, max_per_row) with fields first, last, peak, peak_db; synchronous."""
+        K = self.detect_shape()[0]
+        r = np.asarray(rows, dtype=np.float32)
+        r = r.reshape(-1, r.shape[-1])
+        if r.shape[1] != self.n_win:
+            if r.shape[1] != self.row_length:
+                raise ValueError("rows must be n_win or row_length wide")
+            full = np.full((r.shape[0], self.n_win), np.nan, dtype=np.float32)  # the tail is never read
+            full[:, :r.shape[1]] = r
+            r = full
+        r = np.ascontiguousarray(r)
+        count = r.shape[0]
+        floor = np.empty(count, dtype=np.float32)
+        found = np.empty(count, dtype=np.int32)
+        events = np.empty((count, K), dtype=EMISSION_DTYPE)
+        check(self.lib.zfft_detect(self._plan, r.ctypes.data_as(ctypes.c_void_p), count,
+                                   floor.ctypes.data_as(ctypes.c_void_p), found.ctypes.data_as(ctypes.c_void_p),
+                                   events.ctypes.data_as(ctypes.c_void_p)), "zfft_detect")
+        return floor, found, events
+
+    def detect_device(self, d_rows_ptr: int, count: int, d_floor_ptr: int, d_found_ptr: int,
+                      d_events_ptr: int, stream: int = 0) -> None:
+        """`count` device rows of n_win floats (e.g. what process_device wrote) into device outputs:
+        count floats, count int32 and count * max_per_row 16-byte records (16-byte aligned);
+        enqueued on `stream`, no sync."""
+        check(self.lib.zfft_detect_device(self._plan, ctypes.c_void_p(d_rows_ptr), int(count),
+                                          ctypes.c_void_p(d_floor_ptr), ctypes.c_void_p(d_found_ptr),
+                                          ctypes.c_void_p(d_events_ptr), ctypes.c_void_p(stream or None)),
+              "zfft_detect_device")
+
+    def detect_occupancy(self):
+        """(occ, rows_seen): uint32 counts per column (n_win), how often each was part of an
+        emission, and the rows given since the last reset."""
+        occ = np.empty(self.n_win, dtype=np.uint32)
+        seen = ctypes.c_uint64()
+        check(self.lib.zfft_detect_occupancy(self._plan, occ.ctypes.data_as(ctypes.c_void_p),
+                                             ctypes.byref(seen)), "zfft_detect_occupancy")
+        return occ, int(seen.value)
+
+    def detect_reset(self) -> None:
+        check(self.lib.zfft_detect_reset(self._plan), "zfft_detect_reset")
+
+
+# zfft_emission (include/zfft.h): one record of ZoomFFT.detect
+EMISSION_DTYPE = np.dtype([("first", np.int32), ("last", np.int32), ("peak", np.int32), ("peak_db", np.float32)])
+
 
 _IN_DTYPES = {"complex64": (0, np.complex64, 1), "complex32": (1, np.float16, 2),
               "cu8": (2, np.uint8, 2), "f32": (3, np.float32, 1)}

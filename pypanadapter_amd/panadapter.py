@@ -324,6 +324,80 @@ class Persistence:
         self._need_plan().persistence_reset()
 
 
+class Detector:
+    """Signal detection on a stream of rows, on the device (ZoomFFT.set_detect; the rule is in
+    include/zfft.h): per row the noise floor, the emissions above floor + threshold_db, and per
+    column how often it was part of one.
+
+        det = Detector(threshold_db=12.0)        # row units, 20 log10: 12.04 is 4x in power
+        floor, found, events = det.update(psd_lines(chunk, fs, N, zoom, 1))
+        busy = det.occupancy()                   # float64 (W,), share of the rows seen
+
+    `update` takes one row or (R, W) rows and lazily builds a plan for their width, like
+    `Persistence`; a new width rebuilds it and starts from zeros.  `events` is (R, max_per_row)
+    with fields first, last, peak, peak_db; `frequencies` maps its columns to Hz."""
+
+    def __init__(self, quantile: float = 0.5, threshold_db: float = 12.0, min_width: int = 1,
+                 max_per_row: int = 8, device: int = 0, fs: float = 2.4e6):
+        self.quantile, self.threshold_db = float(quantile), float(threshold_db)
+        self.min_width, self.max_per_row = int(min_width), int(max_per_row)
+        self.device = device
+        self.fs = fs
+        self.width = 0
+        self._plan: ZoomFFT | None = None
+
+    def _ensure(self, width: int):
+        if width != self.width or self._plan is None:
+            self.close()
+            n_win = width + (width & 1)  # a plan's rows are even: an odd width gets a NaN column
+            n_fft = 1 << max(5, (n_win - 1).bit_length())
+            self._plan = ZoomFFT(n_fft, 1, self.fs, n_win=n_win, device=self.device)
+            self._plan.set_detect(self.quantile, self.threshold_db, self.min_width, self.max_per_row)
+            self.width = width
+
+    def _need_plan(self):
+        if self._plan is None:
+            raise AttributeError("the detector's plan is created by the first update")
+        return self._plan
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+            self.width = 0
+
+    def update(self, psd_rows):
+        """(floor float32[R], found int32[R], events[R, max_per_row]) of the rows."""
+        rows = np.asarray(psd_rows, dtype=np.float32)
+        rows = rows.reshape(-1, rows.shape[-1])
+        width = rows.shape[1]
+        self._ensure(width)
+        if self._plan.n_win != width:
+            rows = np.concatenate([rows, np.full((len(rows), 1), np.nan, np.float32)], axis=1)
+        return self._plan.detect(rows)
+
+    @property
+    def rows_seen(self) -> int:
+        return self._need_plan().detect_occupancy()[1]
+
+    def occupancy(self) -> np.ndarray:
+        """float64 occ / max(rows_seen, 1) per column: the share of the rows in which the column
+        was part of an emission."""
+        occ, seen = self._need_plan().detect_occupancy()
+        return occ[:self.width] / float(max(seen, 1))
+
+    def reset(self) -> None:
+        self._need_plan().detect_reset()
+
+    def frequencies(self, fs: float, n_fft: int, zoom: int) -> np.ndarray:
+        """Offset in Hz from the centre (the LO) of every column of a two-sided row of this
+        width: the row is fftshift(P)[N/2 - W/2 : N/2 + W/2] (zfft_plan_row_length), so column j
+        is bin j - W/2 of bins fs / (zoom n_fft) wide."""
+        if not self.width:
+            raise AttributeError("the detector's width is set by the first update")
+        return (np.arange(self.width) - self.width // 2) * (float(fs) / (int(zoom) * int(n_fft)))
+
+
 class Data:
     """pypanadapter_thread.py's `Data` (T:1400-1483) on the pinned double-buffered IQRing
     (SURVEY §8f-1), same calls: the reader thread's `add(chunk)` (T:2191) and the PSD
