@@ -219,8 +219,21 @@ const char *zfft_plan_timing_names(zfft_plan *plan);
  * zfft_process call is judged by its own frame count (host calls are split into batches of
  * about 1 GiB of input -- 418 cfg2 frames); crossovers measured by tools/sweep_schedule.py,
  * tools/sweep_walk.py and tools/fc_ab.py (profiles/r04v, r06k, r06fc).  Default tolerance:
- * path 6 gives the float64 reference's decimated IQ within 6.5e-7 of its peak (measured
- * worst 6.0e-7, tests/test_gpu_fc.py FC_TOL); the PC choices (zoom 8 below 16 frames per call,
+ * path 6 gives the float64 reference's decimated IQ within 6.5e-7 of its peak for content the
+ * filter passes (measured worst 6.0e-7 on noise plus in-band tones, tests/test_gpu_fc.py FC_TOL).
+ * FC applies the response truncated at |k| <= K, a coherent error on top of that: for a carrier
+ * near the last stage's cutoff up to 1.09e-6 of the carrier at 1.04 x the cutoff at zoom 8
+ * (7.7e-7 of it, times the LO's sqrt 2), 2.4e-8 at zoom 4 and 2.4e-8 at zoom 2 (path 7), 1.8e-7
+ * at zoom 16; for a carrier in the stopband <= 7e-8 (the float64 models of
+ * tests/dynrange_ref.py trunc_term, recorded per case in tests/golden/dynrange.json).  On every
+ * path the error scales with the strongest input component, wherever it lies -- not with the
+ * displayed content: a full-scale carrier outside the band leaves an error floor of 1e-7 ... 4e-7
+ * of the carrier on FC and PC (-128 dBc and below), 2e-6 on paths 1 and 2, 1e-5 on XA under in-band
+ * content that may be 100 dB weaker (tests/test_gpu_dynrange.py).  The constants
+ * here were measured on Gaussian noise, whose rms is a third of its peak; a full-scale carrier
+ * on the band edge (rms = peak, on the filter's poles) exceeds them: path 1 3.1e-6 of the
+ * carrier, zoom 4's walk 1.8e-5 (its tiles, whose second FIR sums in float64, 8.2e-6; zoom 8's
+ * tiles 6.6e-6, zoom 2's 6.1e-6), path 7 at zoom 2 7.4e-7.  The PC choices (zoom 8 below 16 frames per call,
  * zoom 4 below 32, zoom 2 below 512) within 6.5e-6, the head of zoom >= 16 (x8 + zoom 2's tiles or the
  * blocked passes) within 7.5e-6 -- the measured worst of the GPU tests + ~20 % (5.35e-6 and
  * 6.02e-6; the walk on the zf_n512_z8 fixture 6.07e-6; tests/test_gpu_pc.py PC_TOL / HEAD_TOL);

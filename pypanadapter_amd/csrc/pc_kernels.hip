@@ -519,13 +519,46 @@ __global__ void __launch_bounds__(256) pc_tail_kernel(const v2f *y2, int64_t y2s
     // tap u multiplies z[2 m + u - C]: centred (C = (G - 1) / 2), or M's z^-8 .. z^16 at zoom 2
     constexpr int C = ZOOM == 2 ? -kPc2M0 : (G - 1) / 2;
     const LP zb = sp + 18 * t + (kPcK2Left - 2 * kU3Base) - C;
+    if constexpr (ZOOM == 4) {
+      // Zoom 4's g1 sums in float64.  g0 and the own-rate sections hand it a carrier near the
+      // band edge (0.1 fs) at 6 x its input amplitude and g1's taps cancel it again: summed in
+      // float32 that leaves 1.8e-5 of a full-scale carrier at 1.04 x the cutoff, 2.7 x what the
+      // tiles are documented to give (tests/test_gpu_dynrange.py).  These tiles are
+      // the automatic schedule for the few frames per call of interactive use, where the launch
+      // and not the 41 taps per output sets the time; the walk keeps its float32 sum.
+      double ur[9], ui[9];
 #pragma unroll
-    for (int p = 0; p < (G + 17) / 2; ++p) {
-      const int j = 2 * p;
-      const v4f w = *(LP4)(zb + j);
-      const v2f x0 = lo2(w), x1 = hi2(w);
+      for (int r = 0; r < 9; ++r) ur[r] = ui[r] = 0.0;
 #pragma unroll
-      for (int r = 0; r < 9; ++r) fir_pair<G>(u[r], taps(), j - 2 * r, x0, x1);
+      for (int p = 0; p < (G + 17) / 2; ++p) {
+        const int j = 2 * p;
+        const v4f w = *(LP4)(zb + j);
+#pragma unroll
+        for (int r = 0; r < 9; ++r) {
+          const int q = j - 2 * r;
+          if (q >= 0 && q < G) {
+            const double g = (double)taps()[q];
+            ur[r] = fma(g, (double)w.x, ur[r]);
+            ui[r] = fma(g, (double)w.y, ui[r]);
+          }
+          if (q + 1 >= 0 && q + 1 < G) {
+            const double g = (double)taps()[q + 1];
+            ur[r] = fma(g, (double)w.z, ur[r]);
+            ui[r] = fma(g, (double)w.w, ui[r]);
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 9; ++r) u[r] = v2f{(float)ur[r], (float)ui[r]};
+    } else {
+#pragma unroll
+      for (int p = 0; p < (G + 17) / 2; ++p) {
+        const int j = 2 * p;
+        const v4f w = *(LP4)(zb + j);
+        const v2f x0 = lo2(w), x1 = hi2(w);
+#pragma unroll
+        for (int r = 0; r < 9; ++r) fir_pair<G>(u[r], taps(), j - 2 * r, x0, x1);
+      }
     }
   }
   __syncthreads();

@@ -43,8 +43,11 @@ def taps(K, gg=None):
     return g[c - K:c + K + 1]
 
 
-def fc_decimate(x, gk, N, dt=np.complex64):
-    """Overlap-save FFT decimation by 8 with the fold; returns outputs m = 0 .. ceil(L/8) - 1."""
+def fc_decimate(x, gk, N, dt=np.complex64, image_gain=None):
+    """Overlap-save FFT decimation by 8 with the fold; returns outputs m = 0 .. ceil(L/8) - 1.
+    image_gain: eight factors on the fold's images (spectrum slices q N/8 ...), all 1 in the
+    decimator; tests/test_dynrange_host.py breaks one on purpose (0: the image left out, -1: the
+    filter table's sign flipped there) to show that its gate notices."""
     K = (len(gk) - 1) // 2
     assert K % 8 == 0 and N % 8 == 0
     L = len(x)
@@ -59,7 +62,10 @@ def fc_decimate(x, gk, N, dt=np.complex64):
     for m0 in range(0, nout, P):
         blk = xp[8 * m0:8 * m0 + N]
         Y = sf.fft(blk) * GN
-        Yf = Y.reshape(8, N // 8).sum(axis=0)
+        Yf = Y.reshape(8, N // 8)
+        if image_gain is not None:
+            Yf = Yf * np.asarray(image_gain, dtype=dt)[:, None]
+        Yf = Yf.sum(axis=0)
         y = sf.ifft(Yf) / 8                  # ifft's 1/(N/8) times 1/8 = 1/N
         # local index i = 8 j + K  ->  j = 0 .. P-1 after shifting by K / 8
         yj = np.roll(y, -(K // 8))[:P]

@@ -19,6 +19,8 @@ digests), rows.npz (float64 rows), inputs.npz (small stored complex64 inputs),
 zoomfft.npz (decimated IQ), waterfall.npz (image snapshots), ring.npz (Data sequences).
 
 Run:  python tools/gen_golden.py
+      python tools/gen_golden.py --dynrange    writes dynrange.json / dynrange.npz and nothing else
+                                               (the strong out-of-band carrier cases, dynrange_main)
 """
 from __future__ import annotations
 
@@ -359,5 +361,47 @@ def main():
     return 0
 
 
+def dynrange_main():
+    """tests/golden/dynrange.json and dynrange.npz, and only them (tests/dynrange_ref.py has the
+    case table and the arithmetic): for the RECORDED zoom 2 / 4 / 8 cases the row of the
+    reference's own update path (the threaded variant's PSD.update: it takes the odd frame
+    lengths) and for every case the input digest, S and the FC forms' truncation terms."""
+    if not os.path.isdir("/root/reference"):
+        print("gen_golden: /root/reference absent, nothing to do")
+        return 0
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dynrange_ref as dr
+    import ref_stub
+    T = ref_stub.load("thread")
+    rows, cases = {}, []
+    for c in dr.CASES:
+        x = dr.case_input(c)
+        meta = dict(c, input_sha256=synth.digest(x))
+        sig = dr.case_signal(c, x)
+        e = dr.e32(sig, c["zoom"], c["fs"], c["f_lo"])
+        base = dr.base_e32(len(sig), c["zoom"])
+        meta.update(E32=e, base_E32=base, S=max(1.0, e / base), trunc=dr.trunc_terms(c, sig))
+        if c["name"] in dr.RECORDED:
+            kw = dict(n_fft=c["n_fft"], zoom=c["zoom"], L=c["n_samples"], fs=c["fs"], window="hamming")
+            assert not c["flip"] and lo_len_ok(kw), c["name"]
+            row = run_T(T, kw, premix(x, c["f_lo"], c["fs"]))
+            assert row.shape == (c["n_win"],) and row.dtype == np.float64, (c["name"], row.shape)
+            rows[c["name"]] = row
+        meta["recorded_row"] = c["name"] in rows
+        assert meta["S"] <= dr.S_CAP, (c["name"], meta["S"])
+        cases.append(meta)
+        print(f"{c['name']:24s} L={c['n_samples']:8d} S={meta['S']:5.2f} E32={e:.2e} base={base:.2e} "
+              f"trunc={ {k: float('%.3g' % v) for k, v in meta['trunc'].items()} }")
+    assert sorted(rows) == sorted(dr.RECORDED)
+    np.savez_compressed(os.path.join(OUT, "dynrange.npz"), **rows)
+    with open(os.path.join(OUT, "dynrange.json"), "w") as fh:
+        json.dump(dict(generator="tools/gen_golden.py --dynrange",
+                       reference="alfille/pypanadapter @ /root/reference (T variant's PSD.update)",
+                       numpy=np.__version__, scipy=__import__("scipy").__version__, cases=cases),
+                  fh, indent=1)
+    print("wrote", len(cases), "dynamic-range cases,", len(rows), "recorded rows")
+    return 0
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(dynrange_main() if sys.argv[1:] == ["--dynrange"] else main())
