@@ -30,7 +30,11 @@ r_fs = A sum(w) / sqrt(fs sum(w^2)) the level of a bin-centred carrier of amplit
 Minkowski's inequality over the segments |r_got - r_ref| <= 2 B r_fs, and Welch's own float32
 error is gated at AMP_TOL of a full-scale bin in PSD, AMP_TOL / 2 in amplitude:
 
-    |r_got - r_ref| <= (2 bound(path, case) + AMP_TOL / 2) r_fs     for every column."""
+    |r_got - r_ref| <= (2 bound(path, case) + AMP_TOL / 2) r_fs     for every column.
+
+The AMP_TOL / 2 term is a flat allowance, not a measurement: the Welch stage's own share is
+measured, against its own float32 yardstick, in tests/test_gpu_welch_dynrange.py
+(tests/welch_dynrange_ref.py)."""
 import json
 import os
 

@@ -21,6 +21,8 @@ zoomfft.npz (decimated IQ), waterfall.npz (image snapshots), ring.npz (Data sequ
 Run:  python tools/gen_golden.py
       python tools/gen_golden.py --dynrange    writes dynrange.json / dynrange.npz and nothing else
                                                (the strong out-of-band carrier cases, dynrange_main)
+      python tools/gen_golden.py --welch-dynrange   writes welch_dynrange.json and nothing else
+                                               (full-scale in-band content, welch_dynrange_main)
 """
 from __future__ import annotations
 
@@ -403,5 +405,27 @@ def dynrange_main():
     return 0
 
 
+def welch_dynrange_main():
+    """tests/golden/welch_dynrange.json, and only it (tests/welch_dynrange_ref.py has the shape
+    table and the arithmetic): per shape its seed and, per frame, the case's name and E32, the
+    float32 yardstick of the Welch gate.  Needs numpy and scipy only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import welch_dynrange_ref as wd
+    shapes = []
+    for s in wd.SHAPES:
+        E = wd.shape_e32(s)
+        assert wd.FACTOR * max(E) <= wd.CAP, (s["name"], max(E))
+        shapes.append(dict(name=s["name"], seed=s["seed"], cases=[wd.case_name(s, f) for f in range(s["frames"])],
+                           E32=[float("%.4g" % e) for e in E]))
+        print(f"{s['name']:44s} E32 {min(E):.2e} .. {max(E):.2e}")
+    with open(os.path.join(OUT, "welch_dynrange.json"), "w") as fh:
+        json.dump(dict(generator="tools/gen_golden.py --welch-dynrange", numpy=np.__version__,
+                       scipy=__import__("scipy").__version__, shapes=shapes), fh, indent=1)
+    print("wrote", len(shapes), "shapes,", sum(len(s["E32"]) for s in shapes), "cases")
+    return 0
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--welch-dynrange"]:
+        sys.exit(welch_dynrange_main())
     sys.exit(dynrange_main() if sys.argv[1:] == ["--dynrange"] else main())
