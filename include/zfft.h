@@ -442,6 +442,81 @@ int zfft_detect(zfft_plan *plan, const float *rows, int32_t count, float *floor_
 int zfft_detect_occupancy(zfft_plan *plan, uint32_t *occ_out, uint64_t *rows_seen);
 int zfft_detect_reset(zfft_plan *plan); /* zeroes occupancy and rows_seen */
 
+/* Display viewport: a second, display-sized image kept on the device, reduced from the rows the
+ * caller pushes as a spectrum analyser's display detector does -- every pixel the max, min or
+ * mean of all the columns and rows that fall into it -- in the model of the ring, persistence
+ * and the detector: nothing is hidden inside zfft_process*, and a plan that never enables it
+ * allocates and launches nothing for it.  The reference-compatible ring (zfft_waterfall_*) is
+ * untouched by all of this.
+ * A row is the first n = zfft_plan_row_length(plan) floats of a stride of n_win.  The rule
+ * (MAX and MIN reproducible bit for bit in numpy float32):
+ *   1. geometry: 0 <= col0 < col1 <= n, span = col1 - col0, 1 <= width <= span (a pixel never
+ *      covers less than one column: no upsampling), 1 <= height <= 8192, height * width <= 2^25,
+ *      1 <= rows_per_line <= 65536, detector one of zfft_view_detector.  Pixel x covers the
+ *      columns [e(x), e(x + 1)), e(x) = col0 + floor(x * span / width) in int64
+ *      (zfft_viewport_edge): bucket sizes differ by at most one.
+ *   2. groups: pushed rows are counted from the enable or the last zfft_viewport_reset, across
+ *      pushes; rows [L m, (L + 1) m), m = rows_per_line, form line L.  A group a push leaves
+ *      incomplete stays pending on the device (`pending` = its rows so far) and a later push
+ *      completes it: any split of the same rows into pushes gives the same lines, bit for bit
+ *      for MAX and MIN, within the row gate (1e-3 dB) for MEAN.
+ *   3. cell value over the set S of m rows x the bucket's columns:
+ *        ZFFT_VIEW_MAX   np.fmax.reduce(S): NaN is ignored, an all-NaN S gives NaN, +-inf take
+ *                        part; whether a zero result is -0.0 or 0.0 is not defined;
+ *        ZFFT_VIEW_MIN   np.fmin.reduce(S), likewise;
+ *        ZFFT_VIEW_MEAN  20 log10(sum_S 10^(v/20) / |S|): rows are 20 log10(PSD), so this is the
+ *                        mean PSD.  Any NaN in S gives NaN, -inf contributes 0, +inf gives +inf,
+ *                        an all-zero sum -inf.  10^(v/20) is float32, the sums are float64 (the
+ *                        pending group's too), in any order.
+ *   4. image: completed lines go into a ring of `height` lines in the waterfall ring's
+ *      convention, img[i] == ring[(i + off) mod height] and off += scroll per line: with scroll
+ *      +1 the newest line is image row height - 1 and the lines above it are older one by one,
+ *      with -1 it is row 0 and the lines below are older (the waterfall ring's scroll +1 keeps
+ *      the reference's roll, newest at row H - 2; the viewport does not).  The direction is cfg.scroll as
+ *      it is at the enable or the reset (zfft_waterfall_reset changes cfg.scroll).  Lines not yet
+ *      written are NaN; no grid, no tick stamps.  When one push completes more than `height`
+ *      lines the last `height` remain; `lines` and the hold traces count all of them.
+ *   5. traces, `width` floats each: last = the newest completed line; max_hold / min_hold = the
+ *      per-pixel fmax / fmin of every line completed since the enable, the reset or
+ *      zfft_viewport_hold_reset.  All NaN before the first line.
+ *   6. render: zfft_waterfall_render's pixel formula with the plan's colormap and levels
+ *      (zfft_waterfall_colormap / _levels need no ring: a plan too narrow for the ring, n_win
+ *      < 40, can have a viewport); NaN has alpha 0.
+ * Every zfft_viewport_* call on a plan with the viewport off returns ZFFT_EINVAL
+ * (zfft_viewport_shape after reporting 0 x 0).  With zfft_plan_timing on, a push reports its
+ * kernels as "view_lines", then "view_finish" when a second launch merged the pending group,
+ * a split group's slices or the workgroups' hold partials. */
+enum zfft_view_detector { ZFFT_VIEW_MAX = 0, ZFFT_VIEW_MIN = 1, ZFFT_VIEW_MEAN = 2 };
+/* height = 0 (default): off, frees everything.  Valid arguments (rule 1) allocate the ring, the
+ * traces and the pending accumulator, all NaN / empty; anything else ZFFT_EINVAL.  Re-enabling
+ * with any parameters resets the viewport: rows are not kept, so older lines cannot be reduced
+ * again to a new geometry. */
+int zfft_plan_viewport(zfft_plan *plan, int32_t height, int32_t width, int32_t col0, int32_t col1,
+                       int32_t detector, int32_t rows_per_line);
+/* No plan, no GPU: e(x) of rule 1 for 0 <= x <= width; -1 for invalid arguments. */
+int64_t zfft_viewport_edge(int32_t col0, int32_t col1, int32_t width, int32_t x);
+int zfft_viewport_shape(const zfft_plan *plan, int32_t *height, int32_t *width);
+/* count rows of stride n_win on the device; only columns [col0, col1) are read.  Enqueued on
+ * hip_stream, no sync; ordered after earlier work on that stream (as zfft_persistence_push_device). */
+int zfft_viewport_push_device(zfft_plan *plan, const float *d_rows, int32_t count, void *hip_stream);
+int zfft_viewport_push(zfft_plan *plan, const float *rows /* host */, int32_t count);  /* synchronous */
+/* rows pushed, lines completed and the pending group's rows since the enable / reset; any NULL */
+int zfft_viewport_state(zfft_plan *plan, uint64_t *rows_seen, uint64_t *lines, int32_t *pending);
+/* these wait for the plan's enqueued pushes.  img_out height*width floats in image order;
+ * last / max_hold / min_hold width floats each, NULL = skip */
+int zfft_viewport_read(zfft_plan *plan, float *img_out);
+int zfft_viewport_traces(zfft_plan *plan, float *last, float *max_hold, float *min_hold);
+int zfft_viewport_hold_reset(zfft_plan *plan); /* max_hold and min_hold back to NaN, nothing else */
+/* image, traces, pending group and counters as after the enable; re-reads cfg.scroll */
+int zfft_viewport_reset(zfft_plan *plan);
+/* RGBA8, height*width*4 bytes: into device memory on hip_stream (no sync), or to the host */
+int zfft_viewport_render_device(zfft_plan *plan, uint8_t *d_rgba, void *hip_stream);
+int zfft_viewport_render(zfft_plan *plan, uint8_t *rgba_out);
+/* The per-line display in one round trip (as zfft_waterfall_push_render): count >= 0 host rows
+ * staged in page-locked memory and pushed, the image rendered and copied, one wait.  An image of
+ * at most 4 MiB is written straight into a page-locked rgba_out (zfft_host_alloc). */
+int zfft_viewport_push_render(zfft_plan *plan, const float *rows, int32_t count, uint8_t *rgba_out);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

@@ -42,6 +42,8 @@ WINDOW_ALIASES = {
 WIN_ARRAY = 100
 # enum zfft_average: how a frame's Welch segments combine (zfft_plan_average)
 AVERAGES = {"mean": 0, "median": 1, "max": 2}
+# enum zfft_view_detector: what a viewport pixel shows of its bucket (zfft_plan_viewport)
+VIEW_DETECTORS = {"max": 0, "min": 1, "mean": 2}
 
 
 class zfft_config(ctypes.Structure):
@@ -71,6 +73,10 @@ EXPORTS = [
     "zfft_persistence_push", "zfft_persistence_decay", "zfft_persistence_reset", "zfft_persistence_read",
     "zfft_plan_detect", "zfft_detect_shape", "zfft_detect_device", "zfft_detect", "zfft_detect_occupancy",
     "zfft_detect_reset",
+    "zfft_plan_viewport", "zfft_viewport_edge", "zfft_viewport_shape", "zfft_viewport_push_device",
+    "zfft_viewport_push", "zfft_viewport_state", "zfft_viewport_read", "zfft_viewport_traces",
+    "zfft_viewport_hold_reset", "zfft_viewport_reset", "zfft_viewport_render_device", "zfft_viewport_render",
+    "zfft_viewport_push_render",
 ]
 
 _lib = None
@@ -162,6 +168,20 @@ def load(path: str = ""):
         "zfft_detect": (ctypes.c_int, [P, P, I32, P, P, P]),
         "zfft_detect_occupancy": (ctypes.c_int, [P, P, ctypes.POINTER(ctypes.c_uint64)]),
         "zfft_detect_reset": (ctypes.c_int, [P]),
+        "zfft_plan_viewport": (ctypes.c_int, [P, I32, I32, I32, I32, I32, I32]),
+        "zfft_viewport_edge": (I64, [I32, I32, I32, I32]),
+        "zfft_viewport_shape": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+        "zfft_viewport_push_device": (ctypes.c_int, [P, P, I32, P]),
+        "zfft_viewport_push": (ctypes.c_int, [P, P, I32]),
+        "zfft_viewport_state": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(I32)]),
+        "zfft_viewport_read": (ctypes.c_int, [P, P]),
+        "zfft_viewport_traces": (ctypes.c_int, [P, P, P, P]),
+        "zfft_viewport_hold_reset": (ctypes.c_int, [P]),
+        "zfft_viewport_reset": (ctypes.c_int, [P]),
+        "zfft_viewport_render_device": (ctypes.c_int, [P, P, P]),
+        "zfft_viewport_render": (ctypes.c_int, [P, P]),
+        "zfft_viewport_push_render": (ctypes.c_int, [P, P, I32, P]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

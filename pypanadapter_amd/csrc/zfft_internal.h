@@ -1,7 +1,7 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
 // zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and
-// the HIP kernels (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, detect_kernels.hip).  Not part
-// of the C-ABI.
+// the HIP kernels (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, detect_kernels.hip,
+// view_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
+#include "zfft_view_plan.h"    // the viewport's forms (ViewForm)
 #include "zfft_welch_plan.h"  // the Welch forms' domains (kMaxLdsFft, kDifMin / kDifMax, ...), WelchSel
 
 struct zfft_emission;  // zfft.h
@@ -414,6 +415,29 @@ struct DetectGeom {
 hipError_t launch_detect_rows(const float *rows, int64_t row_stride, int count, const DetectGeom &g,
                               const DetectForm &form, float *floor_out, int32_t *found_out,
                               zfft_emission *events, unsigned *occ, hipStream_t st);
+// Display viewport (zfft.h's rule; view_kernels.hip): one push of `count` rows of stride n_win
+// into the ring of H lines of `width` pixels, pixel x the columns [col0 + x span / width,
+// col0 + (x + 1) span / width).  The push continues a group of `pending` rows (its accumulator
+// in `pend`: width floats, or width float64 linear sums for det 2) and completes ncomp =
+// (pending + count) / m lines, line r into the slot that is image row H - 1 (scroll +1) or 0
+// (scroll -1) after off0 has advanced by (r + 1) scroll.  traces: last,
+// max_hold, min_hold, width floats each.  `f` is choose_view's for the push (refused otherwise).
+struct ViewGeom {
+  int n_win, col0, span, width;
+  int det, m;               // zfft_view_detector, rows_per_line
+  int H, off0, scroll;
+  int count, pending, ncomp;
+  int direct;               // view_direct: launch_view_lines alone does the whole push
+};
+// One workgroup per tile and no partial group in the push: the lines kernel updates the hold
+// traces itself and there is no finishing launch.
+bool view_direct(const ViewGeom &g, const ViewForm &f);
+size_t view_scratch_bytes(const ViewForm &f, int width);
+hipError_t launch_view_lines(const float *rows, const ViewGeom &g, const ViewForm &f, float *ring, float *traces,
+                             void *scratch, size_t scratch_bytes, hipStream_t st);
+hipError_t launch_view_finish(const ViewGeom &g, const ViewForm &f, float *ring, float *traces, void *pend,
+                              const void *scratch, size_t scratch_bytes, hipStream_t st);
+hipError_t launch_view_fill(float *p, int64_t n, float v, hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

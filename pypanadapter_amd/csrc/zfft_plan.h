@@ -1,6 +1,6 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
-// zfft_detect.cpp).  Not part of the C-ABI.
+// zfft_detect.cpp, zfft_viewport.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -123,6 +123,17 @@ struct zfft_plan {
   float dt_thr = 0.f;
   uint64_t dt_rows = 0;
   DevBuf dt_occ, dt_stage, dt_out;
+  // display viewport (zfft_plan_viewport; zfft_viewport.cpp): vw_h = 0 is off (no buffer).  A
+  // ring of vw_h lines of vw_w pixels in the waterfall ring's convention (vw_off, vw_scroll),
+  // the traces last / max_hold / min_hold (3 x vw_w floats), the pending group's accumulator
+  // (vw_w floats, or float64 linear sums for MEAN) and the scratch of a push's partials.  The
+  // counters are host side: pushes are in call order
+  int vw_h = 0, vw_w = 0, vw_c0 = 0, vw_c1 = 0, vw_det = 0, vw_m = 1, vw_scroll = 1;
+  int64_t vw_off = 0;
+  uint64_t vw_rows = 0, vw_lines = 0;
+  int vw_pending = 0;
+  int vw_kind = 0;                 // ViewForm::kind of the last push (test hook zfft__plan_view_form)
+  DevBuf vw_ring, vw_img, vw_tr, vw_pend, vw_scratch, vw_stage, vw_rgba;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the
@@ -166,6 +177,14 @@ int row_length(const zfft_plan *p);  // valid entries per row
 int64_t lines_per_frame(const zfft_plan *p, int64_t L);
 // A NULL stream handle means HIP's default (null) stream, as everywhere in HIP.
 inline hipStream_t pick_stream(zfft_plan *, void *s) { return (hipStream_t)s; }
+
+// --- zfft_waterfall.cpp ---
+// The colormap LUT on the device (built and uploaded on first use, on st) and makeARGB's levels
+// as waterfall_render_kernel takes them; needs no ring.
+int render_setup(zfft_plan *p, hipStream_t st, double *lo, double *scale);
+// An image up to this size is written straight into a page-locked host destination by the
+// kernel; a larger one goes through a device buffer and one copy.
+constexpr size_t kDisplayZeroCopyMax = (size_t)4 << 20;
 
 // --- zfft_decim.cpp ---
 // Stage lengths: n_0 = L, n_{k+1} = ceil(n_k / 2)  (decimate(...)[::2]).

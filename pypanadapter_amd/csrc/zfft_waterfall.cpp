@@ -196,11 +196,10 @@ int zfft_waterfall_get_levels(const zfft_plan *p, double *minlev, double *maxlev
 
 }  // extern "C"
 
-namespace {
 // The colormap LUT on the device (built and uploaded on first use, on st) and makeARGB's
 // levels (pyqtgraph functions.py): equal levels -> max = nextafter(max, 2 max); scale = lut
 // size / (max - min) (1 when the range is 0)
-int render_setup(zfft_plan *p, hipStream_t st, double *lo, double *scale) {
+int zfft::render_setup(zfft_plan *p, hipStream_t st, double *lo, double *scale) {
   if (!p->lut_ready) {
     build_lut(p->cmap.c_str(), p->lut);
     p->lut_ready = true;
@@ -220,10 +219,10 @@ int render_setup(zfft_plan *p, hipStream_t st, double *lo, double *scale) {
   return ZFFT_OK;
 }
 
+namespace {
 // zfft_waterfall_push_render / _push_read64: count host rows pushed, then the image emitted
 // (RGBA8 or float64) and copied to the host -- one kernel for the per-line case, one copy, one
 // wait.  The rows are staged in page-locked memory the kernels read in place.
-constexpr size_t kDisplayZeroCopyMax = (size_t)4 << 20;
 int push_emit(zfft_plan *p, const float *rows, int32_t count, bool f64, void *host_out) {
   int rc = enter(p);
   if (rc) return rc;

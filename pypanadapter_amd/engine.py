@@ -516,6 +516,119 @@ class ZoomFFT:
     def detect_reset(self) -> None:
         check(self.lib.zfft_detect_reset(self._plan), "zfft_detect_reset")
 
+    # ---------------------------------------------------------------- display viewport
+    def set_viewport(self, height: int, width: int, col0: int = 0, col1: int | None = None,
+                     detector: str = "max", rows_per_line: int = 1) -> None:
+        """The display viewport (zfft_plan_viewport): a (height, width) image on the device, fed by
+        `viewport_push*`.  Pixel x shows the `detector` ("max", "min" or "mean", the mean PSD) of
+        the columns [e(x), e(x+1)) of [col0, col1) (col1 None: row_length) over `rows_per_line`
+        consecutive rows; width <= col1 - col0.  Rendered through the plan's colormap and levels;
+        also keeps the traces last / max hold / min hold at that width.  Resets the viewport;
+        height = 0 turns it off and frees it.  The rule is in include/zfft.h."""
+        if detector not in _lib.VIEW_DETECTORS:
+            raise ValueError(f"detector must be one of {sorted(_lib.VIEW_DETECTORS)}")
+        c1 = self.row_length if col1 is None else int(col1)
+        check(self.lib.zfft_plan_viewport(self._plan, int(height), int(width), int(col0), c1,
+                                          _lib.VIEW_DETECTORS[detector], int(rows_per_line)), "zfft_plan_viewport")
+        self.__dict__.pop("_view_slots", None)
+
+    def viewport_shape(self):
+        h, w = ctypes.c_int32(), ctypes.c_int32()
+        check(self.lib.zfft_viewport_shape(self._plan, ctypes.byref(h), ctypes.byref(w)), "zfft_viewport_shape")
+        return h.value, w.value
+
+    def _full_rows(self, rows) -> np.ndarray:
+        """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row), as
+        C-contiguous float32 of n_win columns."""
+        r = np.asarray(rows, dtype=np.float32)
+        r = r.reshape(-1, r.shape[-1])
+        if r.shape[1] != self.n_win:
+            if r.shape[1] != self.row_length:
+                raise ValueError("rows must be n_win or row_length wide")
+            full = np.full((r.shape[0], self.n_win), np.nan, dtype=np.float32)  # the tail is never read
+            full[:, :r.shape[1]] = r
+            r = full
+        return np.ascontiguousarray(r)
+
+    def viewport_push(self, rows) -> None:
+        """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row),
+        reduced into the viewport; synchronous."""
+        r = self._full_rows(rows)
+        check(self.lib.zfft_viewport_push(self._plan, r.ctypes.data_as(ctypes.c_void_p), r.shape[0]),
+              "zfft_viewport_push")
+
+    def viewport_push_device(self, d_rows_ptr: int, count: int, stream: int = 0) -> None:
+        """`count` device rows of n_win floats (e.g. what process_device wrote), enqueued on
+        `stream`, no sync."""
+        check(self.lib.zfft_viewport_push_device(self._plan, ctypes.c_void_p(d_rows_ptr), int(count),
+                                                 ctypes.c_void_p(stream or None)), "zfft_viewport_push_device")
+
+    def viewport_state(self):
+        """(rows_seen, lines, pending): rows pushed, lines completed and the rows of the pending
+        group since the enable or the last reset."""
+        seen, lines, pend = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int32()
+        check(self.lib.zfft_viewport_state(self._plan, ctypes.byref(seen), ctypes.byref(lines),
+                                           ctypes.byref(pend)), "zfft_viewport_state")
+        return int(seen.value), int(lines.value), int(pend.value)
+
+    def viewport_image(self) -> np.ndarray:
+        """float32 (height, width) in image order; lines not yet written are NaN."""
+        img = np.empty(self.viewport_shape(), dtype=np.float32)
+        check(self.lib.zfft_viewport_read(self._plan, img.ctypes.data_as(ctypes.c_void_p)), "zfft_viewport_read")
+        return img
+
+    def viewport_traces(self):
+        """(last, max_hold, min_hold), float32 (width,) each; NaN before the first line."""
+        w = self.viewport_shape()[1]
+        t = np.empty((3, w), dtype=np.float32)
+        check(self.lib.zfft_viewport_traces(self._plan, *(t[k].ctypes.data_as(ctypes.c_void_p) for k in range(3))),
+              "zfft_viewport_traces")
+        return t[0], t[1], t[2]
+
+    def viewport_hold_reset(self) -> None:
+        check(self.lib.zfft_viewport_hold_reset(self._plan), "zfft_viewport_hold_reset")
+
+    def viewport_reset(self) -> None:
+        """Image, traces, pending group and counters as after `set_viewport`; the scroll direction
+        is read again (`waterfall_reset` changes it)."""
+        check(self.lib.zfft_viewport_reset(self._plan), "zfft_viewport_reset")
+
+    def _viewport_out(self, out):
+        h, w = self.viewport_shape()
+        if out is None:
+            slots = self.__dict__.get("_view_slots")
+            if not slots or slots[0][0].shape != (h, w, 4):
+                slots = self._view_slots = [[pinned_empty((h, w, 4), np.uint8) for _ in range(2)], 0]
+            out = slots[0][slots[1] & 1]
+            slots[1] += 1
+        elif out.shape != (h, w, 4) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint8 array of shape {(h, w, 4)}")
+        return out
+
+    def viewport_render(self, out: np.ndarray | None = None) -> np.ndarray:
+        """RGBA uint8 (height, width, 4) of the viewport through the plan's colormap and levels;
+        NaN (lines not yet written) has alpha 0.  `out` as in `waterfall_render`."""
+        out = self._viewport_out(out)
+        check(self.lib.zfft_viewport_render(self._plan, out.ctypes.data_as(ctypes.c_void_p)), "zfft_viewport_render")
+        return out
+
+    def viewport_render_device(self, d_rgba_ptr: int, stream: int = 0) -> None:
+        """RGBA8 pixels of the viewport into device memory (height*width*4 bytes), enqueued on `stream`."""
+        check(self.lib.zfft_viewport_render_device(self._plan, ctypes.c_void_p(d_rgba_ptr),
+                                                   ctypes.c_void_p(stream or None)), "zfft_viewport_render_device")
+
+    def viewport_push_render(self, rows, out: np.ndarray | None = None) -> np.ndarray:
+        """`rows` (host rows as in `viewport_push`, or None) pushed, then the RGBA image, in one
+        round trip (zfft_viewport_push_render): the per-line display call."""
+        out = self._viewport_out(out)
+        if rows is None:
+            count, ptr = 0, None
+        else:
+            r = self._full_rows(rows)
+            count, ptr = r.shape[0], r.ctypes.data
+        check(self.lib.zfft_viewport_push_render(self._plan, ptr, count, out.ctypes.data), "zfft_viewport_push_render")
+        return out
+
 
 # zfft_emission (include/zfft.h): one record of ZoomFFT.detect
 EMISSION_DTYPE = np.dtype([("first", np.int32), ("last", np.int32), ("peak", np.int32), ("peak_db", np.float32)])

@@ -398,6 +398,119 @@ class Detector:
         return (np.arange(self.width) - self.width // 2) * (float(fs) / (int(zoom) * int(n_fft)))
 
 
+class Viewport:
+    """A display-sized view of a stream of rows, reduced on the device (ZoomFFT.set_viewport; the
+    rule is in include/zfft.h): every pixel the max, min or mean PSD of the bucket of columns and
+    the `rows_per_line` rows that fall into it, so a 1920 x 1080 widget shows every narrow or
+    short emission of rows far wider and faster than the screen.
+
+        view = Viewport(1080, 1920, detector="max", rows_per_line=16)
+        view.levels(-220.0, -120.0)
+        view.update(psd_lines(chunk, fs, N, zoom, 1))
+        rgba = view.render()                    # uint8 (1080, 1920, 4) for an ImageItem
+        last, max_hold, min_hold = view.traces()
+
+    `update` takes one row or (R, W) rows and lazily builds a plan for their width, like
+    `Persistence`; a new width rebuilds it and starts empty.  The view's `width` may not exceed
+    the columns it covers ([col0, col1), default the whole row)."""
+
+    def __init__(self, height: int, width: int, detector: str = "max", rows_per_line: int = 1,
+                 col0: int = 0, col1: int | None = None, scroll: int = 1, colormap: str = "Default",
+                 device: int = 0, fs: float = 2.4e6):
+        self.height, self.width = int(height), int(width)
+        self.detector, self.rows_per_line = detector, int(rows_per_line)
+        self.col0, self.col1 = int(col0), col1
+        self.scroll, self.colormap = int(scroll), colormap
+        self.device = device
+        self.fs = fs
+        self.cols = 0
+        self._levels = None
+        self._plan: ZoomFFT | None = None
+
+    def _ensure(self, cols: int):
+        if cols != self.cols or self._plan is None:
+            self.close()
+            n_win = cols + (cols & 1)  # a plan's rows are even: an odd width gets a NaN column
+            n_fft = 1 << max(5, (n_win - 1).bit_length())
+            plan = ZoomFFT(n_fft, 1, self.fs, n_win=n_win, scroll=self.scroll, device=self.device)
+            try:
+                plan.set_viewport(self.height, self.width, self.col0, cols if self.col1 is None else self.col1,
+                                  self.detector, self.rows_per_line)
+                plan.waterfall_colormap(self.colormap)
+                if self._levels is not None:
+                    plan.waterfall_levels(*self._levels)
+            except Exception:
+                plan.close()
+                raise
+            self._plan = plan
+            self.cols = cols
+
+    def _need_plan(self):
+        if self._plan is None:
+            raise AttributeError("the viewport's image is created by the first update")
+        return self._plan
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+            self.cols = 0
+
+    def levels(self, low: float | None = None, high: float | None = None):
+        """Set (when given) and return the render levels (low, high)."""
+        if low is not None:
+            self._levels = (float(low), float(high))
+            if self._plan is not None:
+                self._plan.waterfall_levels(*self._levels)
+        if self._plan is not None:
+            return self._plan.waterfall_levels()
+        return self._levels if self._levels is not None else (-220.0, -120.0)
+
+    def update(self, psd_rows) -> None:
+        rows = np.asarray(psd_rows, dtype=np.float32)
+        rows = rows.reshape(-1, rows.shape[-1])
+        cols = rows.shape[1]
+        self._ensure(cols)
+        if self._plan.n_win != cols:
+            rows = np.concatenate([rows, np.full((len(rows), 1), np.nan, np.float32)], axis=1)
+        self._plan.viewport_push(rows)
+
+    def image(self) -> np.ndarray:
+        """float32 (height, width); lines not yet written are NaN."""
+        return self._need_plan().viewport_image()
+
+    def render(self, out: np.ndarray | None = None) -> np.ndarray:
+        """RGBA uint8 (height, width, 4); see ZoomFFT.waterfall_render for the reuse of the
+        returned array."""
+        return self._need_plan().viewport_render(out)
+
+    def traces(self):
+        """(last, max_hold, min_hold), float32 (width,) each."""
+        return self._need_plan().viewport_traces()
+
+    @property
+    def state(self):
+        """(rows_seen, lines, pending)."""
+        return self._need_plan().viewport_state()
+
+    def hold_reset(self) -> None:
+        self._need_plan().viewport_hold_reset()
+
+    def reset(self) -> None:
+        self._need_plan().viewport_reset()
+
+    def frequencies(self, fs: float, n_fft: int, zoom: int) -> np.ndarray:
+        """Offset in Hz from the centre (the LO) of every pixel: the mean of its bucket's columns
+        under `Detector.frequencies`' mapping of a two-sided row of this width (column j is bin
+        j - W/2 of bins fs / (zoom n_fft) wide)."""
+        if not self.cols:
+            raise AttributeError("the viewport's columns are set by the first update")
+        c1 = self.cols if self.col1 is None else int(self.col1)
+        e = self.col0 + np.arange(self.width + 1, dtype=np.int64) * (c1 - self.col0) // self.width
+        centre = (e[:-1] + e[1:] - 1) / 2.0
+        return (centre - self.cols // 2) * (float(fs) / (int(zoom) * int(n_fft)))
+
+
 class Data:
     """pypanadapter_thread.py's `Data` (T:1400-1483) on the pinned double-buffered IQRing
     (SURVEY §8f-1), same calls: the reader thread's `add(chunk)` (T:2191) and the PSD
