@@ -490,7 +490,7 @@ enum zfft_view_detector { ZFFT_VIEW_MAX = 0, ZFFT_VIEW_MIN = 1, ZFFT_VIEW_MEAN =
 /* height = 0 (default): off, frees everything.  Valid arguments (rule 1) allocate the ring, the
  * traces and the pending accumulator, all NaN / empty; anything else ZFFT_EINVAL.  Re-enabling
  * with any parameters resets the viewport: rows are not kept, so older lines cannot be reduced
- * again to a new geometry. */
+ * again to a new geometry (the row history below keeps them: zfft_history_replay_viewport). */
 int zfft_plan_viewport(zfft_plan *plan, int32_t height, int32_t width, int32_t col0, int32_t col1,
                        int32_t detector, int32_t rows_per_line);
 /* No plan, no GPU: e(x) of rule 1 for 0 <= x <= width; -1 for invalid arguments. */
@@ -516,6 +516,88 @@ int zfft_viewport_render(zfft_plan *plan, uint8_t *rgba_out);
  * staged in page-locked memory and pushed, the image rendered and copied, one wait.  An image of
  * at most 4 MiB is written straight into a page-locked rgba_out (zfft_host_alloc). */
 int zfft_viewport_push_render(zfft_plan *plan, const float *rows, int32_t count, uint8_t *rgba_out);
+
+/* Row history: the rows the caller pushes kept on the device in a ring of capacity_rows rows, as
+ * float32 or quantised to 16- or 8-bit codes on a fixed level scale, so that what has scrolled
+ * past can be reduced again -- to another window of columns, another rows_per_line, another
+ * detector, an older stretch of time -- which the viewport alone cannot do.  In the model of the
+ * ring, persistence, the detector and the viewport: nothing is hidden inside zfft_process*, and
+ * a plan that never enables it allocates and launches nothing for it.
+ * A row is the first n = zfft_plan_row_length(plan) floats of a stride of n_win; the store holds
+ * those n columns (capacity_rows x n x {4, 2, 1} bytes, each row padded to a multiple of 16
+ * elements).  The rule:
+ *   1. rows are numbered from 0 since the enable or the last zfft_history_reset, across pushes;
+ *      rows_seen grows by `count` with every push.  The store keeps the last min(rows_seen,
+ *      capacity) rows, oldest = rows_seen - that; a push of more than capacity rows keeps its
+ *      last capacity.
+ *   2. quantiser (float32 throughout, reproducible bit for bit in numpy float32; K = 254 for U8,
+ *      65534 for U16): lo = (float)db_min, inv = (float)(K / (db_max - db_min)), step =
+ *      (float)((db_max - db_min) / K), both divisions in double and rounded once.
+ *        pack    NaN -> code 0; otherwise t = (v - lo) * inv (a float32 difference, then a
+ *                float32 product) and code = 1 + (int)rintf(fminf(fmaxf(t, 0), K)), ties to even:
+ *                -inf and every level at or below db_min give code 1, +inf and every level at or
+ *                above db_max give code K + 1.
+ *        unpack  code 0 -> NaN; otherwise lo + (float)(code - 1) * step, a float32 product, then
+ *                a float32 sum, never a fused multiply-add.
+ *      The code does not decrease with v and the value does not decrease with the code, pack(
+ *      unpack(c)) == c for every code, and inside [db_min, db_max] the round trip is off by at
+ *      most 0.513 step.  ZFFT_HISTORY_F32 stores and returns the value unchanged (a NaN comes
+ *      back as a NaN) and ignores the two levels.  zfft_history_codes / _values are the quantiser
+ *      itself, on the host.
+ *   3. read: the unpacked rows [first, first + count) as float rows of stride n_win, valid input
+ *      to zfft_viewport_push_device, zfft_persistence_push_device and zfft_detect_device on the
+ *      same stream.  ZFFT_EINVAL unless oldest <= first and first + count <= rows_seen.  Columns
+ *      at or beyond n are left untouched on the device and written as NaN on the host path.
+ *   4. view: rule 1 and rule 3 of zfft_plan_viewport applied to the unpacked rows v', with no
+ *      state: the window's geometry limits are the viewport's (0 <= col0 < col1 <= n, 1 <= width
+ *      <= col1 - col0, 1 <= lines <= 8192, lines * width <= 2^25, 1 <= rows_per_line <= 65536,
+ *      a zfft_view_detector); pixel x covers the columns [e(x), e(x + 1)) of zfft_viewport_edge;
+ *      line L is img[L * width + x], in time order, L = 0 the oldest, over the rows [first + L m,
+ *      first + (L + 1) m), m = rows_per_line.  `first` is signed and may lie before `oldest` or
+ *      run past rows_seen: a line with any row not in the store is all NaN (an incomplete group
+ *      is never shown, as in the viewport).  MAX and MIN are the same bits whatever form ran;
+ *      MEAN = 20 log10(sum 10^(v'/20) / |S|) with 10^x in float32 and the sums in float64.  To
+ *      get the lines a live viewport produced, choose `first` congruent to the row at which that
+ *      viewport was last reset, modulo m.
+ *   5. render: the view through zfft_waterfall_render's pixel formula with the plan's colormap
+ *      and levels, NaN with alpha 0, lines x width x 4 bytes: the bytes zfft_viewport_render
+ *      gives for a viewport that holds the same lines.
+ *   6. replay: zfft_history_replay_viewport(plan, first) needs both features on.  It is
+ *      zfft_viewport_reset followed by the stored rows [max(first, oldest), rows_seen) unpacked
+ *      and pushed in order (through a plan-owned float scratch, in chunks of at most 64 MiB, on
+ *      the plan's stream, one wait at the end): after zfft_plan_viewport with a new geometry it
+ *      rebuilds image, pending group and hold traces, and live pushes carry on from there.
+ * Every zfft_history_* call on a plan with the store off returns ZFFT_EINVAL (zfft_history_shape
+ * after reporting capacity 0).  With zfft_plan_timing on, a push reports its kernel as
+ * "history_pack", a read as "history_unpack" and a view as "history_view", then "history_finish"
+ * when a second launch combined the slices of long groups. */
+enum zfft_history_format { ZFFT_HISTORY_F32 = 0, ZFFT_HISTORY_U16 = 1, ZFFT_HISTORY_U8 = 2 };
+typedef struct zfft_history_window {
+  int64_t first;
+  int32_t rows_per_line, lines, col0, col1, width, detector;
+} zfft_history_window;
+/* capacity_rows = 0 (default): off, frees the store.  Otherwise capacity_rows >= 1, format one of
+ * zfft_history_format and, for U16 / U8, db_min < db_max finite; anything else ZFFT_EINVAL.  An
+ * allocation the device refuses is ZFFT_ENOMEM and leaves the store off.  Re-enabling resets. */
+int zfft_plan_history(zfft_plan *plan, int64_t capacity_rows, int32_t format, double db_min, double db_max);
+int zfft_history_shape(const zfft_plan *plan, int64_t *capacity, int32_t *cols, int32_t *format);
+/* count rows of stride n_win on the device; only the first n columns are read.  Enqueued on
+ * hip_stream, no sync; ordered after earlier work on that stream (as zfft_viewport_push_device). */
+int zfft_history_push_device(zfft_plan *plan, const float *d_rows, int32_t count, void *hip_stream);
+int zfft_history_push(zfft_plan *plan, const float *rows /* host */, int32_t count);  /* synchronous */
+int zfft_history_state(zfft_plan *plan, uint64_t *rows_seen, uint64_t *oldest); /* either may be NULL */
+int zfft_history_read_device(zfft_plan *plan, int64_t first, int32_t count, float *d_rows, void *hip_stream);
+int zfft_history_read(zfft_plan *plan, int64_t first, int32_t count, float *rows_out); /* host, synchronous */
+/* w->lines * w->width floats: into device memory on hip_stream (no sync), or to the host */
+int zfft_history_view_device(zfft_plan *plan, const zfft_history_window *w, float *d_img, void *hip_stream);
+int zfft_history_view(zfft_plan *plan, const zfft_history_window *w, float *img_out);      /* synchronous */
+int zfft_history_render(zfft_plan *plan, const zfft_history_window *w, uint8_t *rgba_out); /* synchronous */
+int zfft_history_replay_viewport(zfft_plan *plan, int64_t first);                          /* synchronous */
+int zfft_history_reset(zfft_plan *plan); /* rows_seen and oldest back to 0 */
+/* No plan, no GPU (like zfft_viewport_edge): rule 2 on n values; format U16 or U8, codes as
+ * uint16 in both.  ZFFT_EINVAL for F32, bad levels or a code above K + 1. */
+int zfft_history_codes(int32_t format, double db_min, double db_max, const float *v, int64_t n, uint16_t *codes_out);
+int zfft_history_values(int32_t format, double db_min, double db_max, const uint16_t *codes, int64_t n, float *v_out);
 
 const char *zfft_last_error(void);
 int zfft_device_count(void);

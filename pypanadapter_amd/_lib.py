@@ -44,6 +44,8 @@ WIN_ARRAY = 100
 AVERAGES = {"mean": 0, "median": 1, "max": 2}
 # enum zfft_view_detector: what a viewport pixel shows of its bucket (zfft_plan_viewport)
 VIEW_DETECTORS = {"max": 0, "min": 1, "mean": 2}
+# enum zfft_history_format: how the row history stores a value (zfft_plan_history)
+HISTORY_FORMATS = {"f32": 0, "u16": 1, "u8": 2}
 
 
 class zfft_config(ctypes.Structure):
@@ -52,6 +54,14 @@ class zfft_config(ctypes.Structure):
         ("window_kind", ctypes.c_int32), ("fs", ctypes.c_double), ("f_lo", ctypes.c_double),
         ("window_param", ctypes.c_double * 2), ("scroll", ctypes.c_int32),
         ("in_dtype", ctypes.c_int32), ("device", ctypes.c_int32), ("flip_input", ctypes.c_int32),
+    ]
+
+
+class zfft_history_window(ctypes.Structure):
+    _fields_ = [
+        ("first", ctypes.c_int64), ("rows_per_line", ctypes.c_int32), ("lines", ctypes.c_int32),
+        ("col0", ctypes.c_int32), ("col1", ctypes.c_int32), ("width", ctypes.c_int32),
+        ("detector", ctypes.c_int32),
     ]
 
 
@@ -77,6 +87,10 @@ EXPORTS = [
     "zfft_viewport_push", "zfft_viewport_state", "zfft_viewport_read", "zfft_viewport_traces",
     "zfft_viewport_hold_reset", "zfft_viewport_reset", "zfft_viewport_render_device", "zfft_viewport_render",
     "zfft_viewport_push_render",
+    "zfft_plan_history", "zfft_history_shape", "zfft_history_push_device", "zfft_history_push",
+    "zfft_history_state", "zfft_history_read_device", "zfft_history_read", "zfft_history_view_device",
+    "zfft_history_view", "zfft_history_render", "zfft_history_replay_viewport", "zfft_history_reset",
+    "zfft_history_codes", "zfft_history_values",
 ]
 
 _lib = None
@@ -119,6 +133,7 @@ def load(path: str = ""):
     lib = ctypes.CDLL(path)
     P, I32, I64, D = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
     cfgp = ctypes.POINTER(zfft_config)
+    winp = ctypes.POINTER(zfft_history_window)
     sig = {
         "zfft_plan_create": (ctypes.c_int, [cfgp, P, ctypes.POINTER(P)]),
         "zfft_plan_destroy": (ctypes.c_int, [P]),
@@ -182,6 +197,20 @@ def load(path: str = ""):
         "zfft_viewport_render_device": (ctypes.c_int, [P, P, P]),
         "zfft_viewport_render": (ctypes.c_int, [P, P]),
         "zfft_viewport_push_render": (ctypes.c_int, [P, P, I32, P]),
+        "zfft_plan_history": (ctypes.c_int, [P, I64, I32, D, D]),
+        "zfft_history_shape": (ctypes.c_int, [P, ctypes.POINTER(I64), ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+        "zfft_history_push_device": (ctypes.c_int, [P, P, I32, P]),
+        "zfft_history_push": (ctypes.c_int, [P, P, I32]),
+        "zfft_history_state": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "zfft_history_read_device": (ctypes.c_int, [P, I64, I32, P, P]),
+        "zfft_history_read": (ctypes.c_int, [P, I64, I32, P]),
+        "zfft_history_view_device": (ctypes.c_int, [P, winp, P, P]),
+        "zfft_history_view": (ctypes.c_int, [P, winp, P]),
+        "zfft_history_render": (ctypes.c_int, [P, winp, P]),
+        "zfft_history_replay_viewport": (ctypes.c_int, [P, I64]),
+        "zfft_history_reset": (ctypes.c_int, [P]),
+        "zfft_history_codes": (ctypes.c_int, [I32, D, D, P, I64, P]),
+        "zfft_history_values": (ctypes.c_int, [I32, D, D, P, I64, P]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

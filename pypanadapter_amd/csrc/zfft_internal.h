@@ -1,7 +1,7 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
 // zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and
 // the HIP kernels (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, detect_kernels.hip,
-// view_kernels.hip).  Not part of the C-ABI.
+// view_kernels.hip, history_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
+#include "zfft_history_plan.h"  // the row history's quantiser and forms (HistQuant, HistForm)
 #include "zfft_view_plan.h"    // the viewport's forms (ViewForm)
 #include "zfft_welch_plan.h"  // the Welch forms' domains (kMaxLdsFft, kDifMin / kDifMax, ...), WelchSel
 
@@ -438,6 +439,35 @@ hipError_t launch_view_lines(const float *rows, const ViewGeom &g, const ViewFor
 hipError_t launch_view_finish(const ViewGeom &g, const ViewForm &f, float *ring, float *traces, void *pend,
                               const void *scratch, size_t scratch_bytes, hipStream_t st);
 hipError_t launch_view_fill(float *p, int64_t n, float v, hipStream_t st);
+// Row history (zfft.h's rule; history_kernels.hip): a ring of `cap` stored rows of `stride`
+// elements (hist_stride(n): float32, uint16 or uint8 codes by q.format), row R of the store's
+// numbering in slot R mod cap, its first n elements the row's columns and the rest padding.
+struct HistStore {
+  void *data;
+  int64_t cap, stride;
+  int n;
+  HistQuant q;
+};
+// rows[i * n_win + j], j < n, i < count, into the slots of the rows row0 + i (one launch; the
+// slots may wrap the ring's end; count <= cap).
+hipError_t launch_history_pack(const float *rows, int n_win, int count, int64_t row0, const HistStore &s,
+                               hipStream_t st);
+// the stored rows row0 + i, i < count, unpacked into rows[i * n_win + j], j < n
+hipError_t launch_history_unpack(const HistStore &s, int64_t row0, int count, int n_win, float *rows, hipStream_t st);
+// A view (zfft_history_window): line L < lines of img (lines x width) over the rows [first + L m,
+// first + (L + 1) m), all NaN unless those lie in [oldest, seen).  `f` is choose_history's for
+// the window (refused otherwise); a sliced form leaves partials in `scratch` and needs
+// launch_history_finish.
+struct HistGeom {
+  int64_t first, oldest, seen;
+  int col0, span, width;
+  int det, m, lines;
+};
+size_t history_scratch_bytes(const HistForm &f, int width);
+hipError_t launch_history_view(const HistStore &s, const HistGeom &g, const HistForm &f, float *img, void *scratch,
+                               size_t scratch_bytes, hipStream_t st);
+hipError_t launch_history_finish(const HistStore &s, const HistGeom &g, const HistForm &f, float *img,
+                                 const void *scratch, size_t scratch_bytes, hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

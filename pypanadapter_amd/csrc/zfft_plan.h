@@ -1,6 +1,6 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
-// zfft_detect.cpp, zfft_viewport.cpp).  Not part of the C-ABI.
+// zfft_detect.cpp, zfft_viewport.cpp, zfft_history.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -134,6 +134,16 @@ struct zfft_plan {
   int vw_pending = 0;
   int vw_kind = 0;                 // ViewForm::kind of the last push (test hook zfft__plan_view_form)
   DevBuf vw_ring, vw_img, vw_tr, vw_pend, vw_scratch, vw_stage, vw_rgba;
+  // row history (zfft_plan_history; zfft_history.cpp): hs_cap = 0 is off (no buffer).  hs_store
+  // holds hs_cap slots of hs_stride elements in hs_q.format, row R in slot R mod hs_cap; hs_seen
+  // counts the rows pushed (host side: pushes are in call order).  hs_stage is the device staging
+  // of host rows (push, read), hs_img / hs_rgba a host view's image and pixels, hs_scratch a sliced
+  // view's partials, hs_replay the float rows of zfft_history_replay_viewport
+  int64_t hs_cap = 0, hs_stride = 0;
+  zfft::HistQuant hs_q;
+  uint64_t hs_seen = 0;
+  int hs_kind = 0;                 // HistForm::kind of the last view (test hook zfft__plan_history_form)
+  DevBuf hs_store, hs_stage, hs_img, hs_rgba, hs_scratch, hs_replay;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the

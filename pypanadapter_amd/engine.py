@@ -629,6 +629,112 @@ class ZoomFFT:
         check(self.lib.zfft_viewport_push_render(self._plan, ptr, count, out.ctypes.data), "zfft_viewport_push_render")
         return out
 
+    # ---------------------------------------------------------------- row history
+    def set_history(self, capacity: int, format: str = "u8", db_min: float = -220.0, db_max: float = -120.0) -> None:
+        """The row history (zfft_plan_history): a ring on the device of the last `capacity` rows
+        given to `history_push*`, stored as float32 ("f32") or as 16- / 8-bit codes ("u16",
+        "u8") on 65534 / 254 equal steps from db_min to db_max (levels outside clamp; NaN keeps a
+        code of its own), so that what has scrolled past can be viewed again with any window, time
+        scale and detector.  Resets the store; capacity = 0 turns it off and frees it.  The rule,
+        the quantiser included, is in include/zfft.h."""
+        if format not in _lib.HISTORY_FORMATS:
+            raise ValueError(f"format must be one of {sorted(_lib.HISTORY_FORMATS)}")
+        check(self.lib.zfft_plan_history(self._plan, int(capacity), _lib.HISTORY_FORMATS[format], float(db_min),
+                                         float(db_max)), "zfft_plan_history")
+
+    def history_shape(self):
+        """(capacity, columns, format)."""
+        cap, cols, fmt = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        check(self.lib.zfft_history_shape(self._plan, ctypes.byref(cap), ctypes.byref(cols), ctypes.byref(fmt)),
+              "zfft_history_shape")
+        return int(cap.value), cols.value, {v: k for k, v in _lib.HISTORY_FORMATS.items()}[fmt.value]
+
+    def history_push(self, rows) -> None:
+        """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row),
+        appended to the store; synchronous."""
+        r = self._full_rows(rows)
+        check(self.lib.zfft_history_push(self._plan, r.ctypes.data_as(ctypes.c_void_p), r.shape[0]),
+              "zfft_history_push")
+
+    def history_push_device(self, d_rows_ptr: int, count: int, stream: int = 0) -> None:
+        """`count` device rows of n_win floats (e.g. what process_device wrote), enqueued on
+        `stream`, no sync."""
+        check(self.lib.zfft_history_push_device(self._plan, ctypes.c_void_p(d_rows_ptr), int(count),
+                                                ctypes.c_void_p(stream or None)), "zfft_history_push_device")
+
+    def history_state(self):
+        """(rows_seen, oldest): rows pushed since the enable or the last reset, and the number of
+        the oldest row still stored; rows [oldest, rows_seen) can be read and viewed."""
+        seen, oldest = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.zfft_history_state(self._plan, ctypes.byref(seen), ctypes.byref(oldest)), "zfft_history_state")
+        return int(seen.value), int(oldest.value)
+
+    def history_rows(self, first: int, count: int) -> np.ndarray:
+        """The stored rows [first, first + count) as the store returns them, float32 (count,
+        n_win); columns at or beyond row_length are NaN."""
+        if int(count) < 1:
+            raise ValueError("count must be at least 1")
+        out = np.empty((int(count), self.n_win), dtype=np.float32)
+        check(self.lib.zfft_history_read(self._plan, int(first), int(count), out.ctypes.data_as(ctypes.c_void_p)),
+              "zfft_history_read")
+        return out
+
+    def history_read_device(self, first: int, count: int, d_rows_ptr: int, stream: int = 0) -> None:
+        """The stored rows [first, first + count) into device rows of n_win floats (valid input to
+        `viewport_push_device`, `persistence_push_device`, `detect_device` on the same stream);
+        enqueued on `stream`, no sync."""
+        check(self.lib.zfft_history_read_device(self._plan, int(first), int(count), ctypes.c_void_p(d_rows_ptr),
+                                                ctypes.c_void_p(stream or None)), "zfft_history_read_device")
+
+    def _history_window(self, first, lines, width, rows_per_line, detector, col0, col1):
+        if detector not in _lib.VIEW_DETECTORS:
+            raise ValueError(f"detector must be one of {sorted(_lib.VIEW_DETECTORS)}")
+        c1 = self.row_length if col1 is None else int(col1)
+        return _lib.zfft_history_window(int(first), int(rows_per_line), int(lines), int(col0), c1, int(width),
+                                        _lib.VIEW_DETECTORS[detector])
+
+    def history_view(self, first: int, lines: int, width: int, rows_per_line: int = 1, detector: str = "max",
+                     col0: int = 0, col1: int | None = None) -> np.ndarray:
+        """float32 (lines, width): line L, in time order, the `detector` of the stored rows
+        [first + L m, first + (L + 1) m), m = rows_per_line, and of the columns [e(x), e(x+1)) of
+        [col0, col1) per pixel, by the viewport's rule.  `first` may be negative or run past
+        rows_seen: a line with a row that is not in the store is NaN."""
+        w = self._history_window(first, lines, width, rows_per_line, detector, col0, col1)
+        img = np.empty((max(int(lines), 0), max(int(width), 0)), dtype=np.float32)
+        check(self.lib.zfft_history_view(self._plan, ctypes.byref(w), img.ctypes.data_as(ctypes.c_void_p)),
+              "zfft_history_view")
+        return img
+
+    def history_view_device(self, d_img_ptr: int, first: int, lines: int, width: int, rows_per_line: int = 1,
+                            detector: str = "max", col0: int = 0, col1: int | None = None, stream: int = 0) -> None:
+        """`history_view` into device memory (lines * width floats), enqueued on `stream`, no sync."""
+        w = self._history_window(first, lines, width, rows_per_line, detector, col0, col1)
+        check(self.lib.zfft_history_view_device(self._plan, ctypes.byref(w), ctypes.c_void_p(d_img_ptr),
+                                                ctypes.c_void_p(stream or None)), "zfft_history_view_device")
+
+    def history_render(self, first: int, lines: int, width: int, rows_per_line: int = 1, detector: str = "max",
+                       col0: int = 0, col1: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """RGBA uint8 (lines, width, 4) of `history_view` through the plan's colormap and levels;
+        NaN has alpha 0."""
+        w = self._history_window(first, lines, width, rows_per_line, detector, col0, col1)
+        shape = (max(int(lines), 0), max(int(width), 0), 4)
+        if out is None:
+            out = np.empty(shape, dtype=np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint8 array of shape {shape}")
+        check(self.lib.zfft_history_render(self._plan, ctypes.byref(w), out.ctypes.data_as(ctypes.c_void_p)),
+              "zfft_history_render")
+        return out
+
+    def history_replay_viewport(self, first: int = 0) -> None:
+        """`viewport_reset`, then the stored rows from max(first, oldest) on pushed into the
+        viewport in order: after `set_viewport` with a new geometry (a zoom, a pan, another
+        detector or time scale) the display is rebuilt from the history and live pushes carry on."""
+        check(self.lib.zfft_history_replay_viewport(self._plan, int(first)), "zfft_history_replay_viewport")
+
+    def history_reset(self) -> None:
+        check(self.lib.zfft_history_reset(self._plan), "zfft_history_reset")
+
 
 # zfft_emission (include/zfft.h): one record of ZoomFFT.detect
 EMISSION_DTYPE = np.dtype([("first", np.int32), ("last", np.int32), ("peak", np.int32), ("peak_db", np.float32)])

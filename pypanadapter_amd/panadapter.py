@@ -511,6 +511,122 @@ class Viewport:
         return (centre - self.cols // 2) * (float(fs) / (int(zoom) * int(n_fft)))
 
 
+class History:
+    """The last `capacity` rows of a stream kept on the device (ZoomFFT.set_history; the rule is
+    in include/zfft.h) as 8- or 16-bit codes on the level scale db_min .. db_max (or as float32),
+    so that a display can zoom, pan, change its time scale or detector and scroll back over what
+    has already passed: `view` reduces any stretch of the stored rows to any pixel grid.
+
+        hist = History(1 << 20, "u8", -160.0, -40.0)
+        hist.update(psd_lines(chunk, fs, N, zoom, 1))
+        first = hist.latest(1080, 16)           # the newest 1080 lines of 16 rows
+        rgba = hist.render(first, 1080, 1920, rows_per_line=16, col0=2000, col1=6000)
+
+    `update` takes one row or (R, W) rows and lazily builds a plan for their width, like
+    `Persistence` and `Viewport`; a new width rebuilds it and starts empty."""
+
+    def __init__(self, capacity: int, format: str = "u8", db_min: float = -220.0, db_max: float = -120.0,
+                 colormap: str = "Default", device: int = 0, fs: float = 2.4e6):
+        self.capacity, self.format = int(capacity), format
+        self.db_min, self.db_max = float(db_min), float(db_max)
+        self.colormap = colormap
+        self.device = device
+        self.fs = fs
+        self.cols = 0
+        self._levels = None
+        self._plan: ZoomFFT | None = None
+
+    def _ensure(self, cols: int):
+        if cols != self.cols or self._plan is None:
+            self.close()
+            n_win = cols + (cols & 1)  # a plan's rows are even: an odd width gets a NaN column
+            n_fft = 1 << max(5, (n_win - 1).bit_length())
+            plan = ZoomFFT(n_fft, 1, self.fs, n_win=n_win, device=self.device)
+            try:
+                plan.set_history(self.capacity, self.format, self.db_min, self.db_max)
+                plan.waterfall_colormap(self.colormap)
+                if self._levels is not None:
+                    plan.waterfall_levels(*self._levels)
+            except Exception:
+                plan.close()
+                raise
+            self._plan = plan
+            self.cols = cols
+
+    def _need_plan(self):
+        if self._plan is None:
+            raise AttributeError("the history's store is created by the first update")
+        return self._plan
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+            self.cols = 0
+
+    def levels(self, low: float | None = None, high: float | None = None):
+        """Set (when given) and return the render levels (low, high)."""
+        if low is not None:
+            self._levels = (float(low), float(high))
+            if self._plan is not None:
+                self._plan.waterfall_levels(*self._levels)
+        if self._plan is not None:
+            return self._plan.waterfall_levels()
+        return self._levels if self._levels is not None else (-220.0, -120.0)
+
+    def update(self, psd_rows) -> None:
+        rows = np.asarray(psd_rows, dtype=np.float32)
+        rows = rows.reshape(-1, rows.shape[-1])
+        cols = rows.shape[1]
+        self._ensure(cols)
+        if self._plan.n_win != cols:
+            rows = np.concatenate([rows, np.full((len(rows), 1), np.nan, np.float32)], axis=1)
+        self._plan.history_push(rows)
+
+    def _c1(self, col1):
+        return self.cols if col1 is None else int(col1)
+
+    def view(self, first: int, lines: int, width: int, rows_per_line: int = 1, detector: str = "max",
+             col0: int = 0, col1: int | None = None) -> np.ndarray:
+        """float32 (lines, width), oldest line first; see ZoomFFT.history_view."""
+        plan = self._need_plan()
+        return plan.history_view(first, lines, width, rows_per_line, detector, col0, self._c1(col1))
+
+    def render(self, first: int, lines: int, width: int, rows_per_line: int = 1, detector: str = "max",
+               col0: int = 0, col1: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """RGBA uint8 (lines, width, 4) of `view` through the colormap and levels."""
+        plan = self._need_plan()
+        return plan.history_render(first, lines, width, rows_per_line, detector, col0, self._c1(col1), out)
+
+    def rows(self, first: int, count: int) -> np.ndarray:
+        """The stored rows [first, first + count) as the store returns them, (count, cols)."""
+        return self._need_plan().history_rows(first, count)[:, :self.cols]
+
+    @property
+    def state(self):
+        """(rows_seen, oldest)."""
+        return self._need_plan().history_state()
+
+    def latest(self, lines: int, rows_per_line: int = 1) -> int:
+        """The `first` whose window of `lines` lines of `rows_per_line` rows ends at rows_seen (it
+        may be negative or lie before `oldest`: those lines are NaN)."""
+        return self.state[0] - int(lines) * int(rows_per_line)
+
+    def reset(self) -> None:
+        self._need_plan().history_reset()
+
+    def frequencies(self, width: int, fs: float, n_fft: int, zoom: int, col0: int = 0,
+                    col1: int | None = None) -> np.ndarray:
+        """Offset in Hz from the centre (the LO) of every pixel of a view of `width` pixels over
+        [col0, col1), as `Viewport.frequencies`."""
+        if not self.cols:
+            raise AttributeError("the history's columns are set by the first update")
+        c1 = self._c1(col1)
+        e = int(col0) + np.arange(int(width) + 1, dtype=np.int64) * (c1 - int(col0)) // int(width)
+        centre = (e[:-1] + e[1:] - 1) / 2.0
+        return (centre - self.cols // 2) * (float(fs) / (int(zoom) * int(n_fft)))
+
+
 class Data:
     """pypanadapter_thread.py's `Data` (T:1400-1483) on the pinned double-buffered IQRing
     (SURVEY §8f-1), same calls: the reader thread's `add(chunk)` (T:2191) and the PSD
