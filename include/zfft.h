@@ -442,6 +442,46 @@ int zfft_detect(zfft_plan *plan, const float *rows, int32_t count, float *floor_
 int zfft_detect_occupancy(zfft_plan *plan, uint32_t *occ_out, uint64_t *rows_seen);
 int zfft_detect_reset(zfft_plan *plan); /* zeroes occupancy and rows_seen */
 
+/* A local noise floor per column (order-statistic CFAR).  The row-global floor is right only
+ * where the floor is flat; under a decimator's roll-off, a shaped passband or beside a strong
+ * wideband emission the quiet part of a row loses its weak emissions and the loud part turns
+ * into one emission.  zfft_plan_detect_local(plan, half_window, guard) judges every column
+ * against an order statistic of the columns around it instead:
+ *   half_window = 0 (then guard must be 0; the default): the row-global floor, everything above.
+ *   Otherwise 1 <= half_window <= 128 and 0 <= guard <= 128.  With h = half_window, gd = guard,
+ *   n = zfft_plan_row_length(plan) and q, threshold_db, min_width, K those of zfft_plan_detect:
+ *   1. reference cells of column j (0 <= j < n): the columns c with gd < |c - j| <= gd + h and
+ *      0 <= c < n.  The window is cut at the row's ends: it neither wraps nor mirrors, so a
+ *      column near an end has fewer cells, all on one side at the very end.  Column j and its gd
+ *      neighbours on either side are never reference cells.
+ *   2. population: the finite values among the reference cells, m_j of them; NaN, +inf and -inf
+ *      are left out, as in the global rule.
+ *   3. floor_j: the value of 0-based rank (int64)floor(q * (double)(m_j - 1)) among them in
+ *      ascending order -- one of the row's own values, bit for bit (which of -0.0 and 0.0 a zero
+ *      floor is, is not defined).  m_j == 0: floor_j = NaN.  numpy: np.sort(w[np.isfinite(w)])[k].
+ *   4. thr_j = floor_j + (float)threshold_db, one float32 addition; column j is on when
+ *      v[j] >= thr_j: +inf is on, NaN and -inf are off, every column with floor_j = NaN is off.
+ *   5. rules 4-7 of zfft_plan_detect hold unchanged: the runs, the records, found, the zeroed
+ *      slots and the occupancy.
+ *   6. floor[i] of zfft_detect* stays the row-global floor (rule 2 of zfft_plan_detect), the
+ *      row's one-number summary.
+ * ZFFT_EINVAL while detection is off and for arguments outside these ranges.  A call zeroes the
+ * occupancy and rows_seen (counts made under two rules do not add).  zfft_plan_detect(...,
+ * max_per_row = 0) puts the mode back to global; a zfft_plan_detect call on a plan that is on
+ * keeps it.  zfft_detect_device and zfft_detect follow the plan's mode; the floors of a pass go
+ * through a device scratch of the plan's, at most 256 MiB (larger calls run in passes), freed
+ * when detection is switched off and never allocated in global mode.  With zfft_plan_timing on a
+ * local-mode call reports "detect_floor" then "detect_rows", once per pass. */
+int zfft_plan_detect_local(zfft_plan *plan, int32_t half_window, int32_t guard);
+int zfft_detect_local_shape(const zfft_plan *plan, int32_t *half_window, int32_t *guard); /* 0, 0: global */
+/* floor_j of rule 3 for `count` rows, as float rows of stride n_win (an SNR, a floor trace on
+ * the display).  A pure function of the rows: no occupancy, no rows_seen.  ZFFT_EINVAL in global
+ * mode.  Device form: columns at or beyond n are left untouched; enqueued on hip_stream, no sync,
+ * ordered after earlier work on that stream; reports "detect_floor".  Host form: those columns
+ * are written as NaN; synchronous. */
+int zfft_detect_floors_device(zfft_plan *plan, const float *d_rows, int32_t count, float *d_floors, void *hip_stream);
+int zfft_detect_floors(zfft_plan *plan, const float *rows, int32_t count, float *floors_out);
+
 /* Display viewport: a second, display-sized image kept on the device, reduced from the rows the
  * caller pushes as a spectrum analyser's display detector does -- every pixel the max, min or
  * mean of all the columns and rows that fall into it -- in the model of the ring, persistence

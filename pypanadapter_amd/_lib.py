@@ -83,6 +83,7 @@ EXPORTS = [
     "zfft_persistence_push", "zfft_persistence_decay", "zfft_persistence_reset", "zfft_persistence_read",
     "zfft_plan_detect", "zfft_detect_shape", "zfft_detect_device", "zfft_detect", "zfft_detect_occupancy",
     "zfft_detect_reset",
+    "zfft_plan_detect_local", "zfft_detect_local_shape", "zfft_detect_floors_device", "zfft_detect_floors",
     "zfft_plan_viewport", "zfft_viewport_edge", "zfft_viewport_shape", "zfft_viewport_push_device",
     "zfft_viewport_push", "zfft_viewport_state", "zfft_viewport_read", "zfft_viewport_traces",
     "zfft_viewport_hold_reset", "zfft_viewport_reset", "zfft_viewport_render_device", "zfft_viewport_render",
@@ -183,6 +184,10 @@ def load(path: str = ""):
         "zfft_detect": (ctypes.c_int, [P, P, I32, P, P, P]),
         "zfft_detect_occupancy": (ctypes.c_int, [P, P, ctypes.POINTER(ctypes.c_uint64)]),
         "zfft_detect_reset": (ctypes.c_int, [P]),
+        "zfft_plan_detect_local": (ctypes.c_int, [P, I32, I32]),
+        "zfft_detect_local_shape": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+        "zfft_detect_floors_device": (ctypes.c_int, [P, P, I32, P, P]),
+        "zfft_detect_floors": (ctypes.c_int, [P, P, I32, P]),
         "zfft_plan_viewport": (ctypes.c_int, [P, I32, I32, I32, I32, I32, I32]),
         "zfft_viewport_edge": (I64, [I32, I32, I32, I32]),
         "zfft_viewport_shape": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),

@@ -35,6 +35,7 @@
 #include <cstdint>
 
 #include "zfft.h"
+#include "zfft_detect_keys.h"  // det_key, det_value, the key ranges
 #include "zfft_internal.h"
 
 namespace zfft {
@@ -42,20 +43,6 @@ namespace zfft {
 namespace {
 
 using u64 = unsigned long long;
-
-// float bits -> uint32 in the floats' order: negative values complemented, the others with the
-// top bit set.  -inf and the NaNs with the sign bit fall below kKeyFiniteLo, +inf and the other
-// NaNs at or above kKeyFiniteHi; the finite values lie between, -0.0 just below 0.0.
-constexpr uint32_t kKeyFiniteLo = 0x00800000u, kKeyFiniteHi = 0xFF800000u;
-constexpr uint32_t kKeyPad = 0xFFFFFFFFu;  // a NaN: the columns beyond row_len, never on, never counted
-
-__device__ __forceinline__ uint32_t det_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float det_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
 
 // The last column of the run of set bits that holds bit `lane` of word wd (m: `words` words).
 __device__ __forceinline__ int run_last(const u64 *m, int words, int wd, int lane) {
@@ -78,12 +65,16 @@ constexpr int kDetectSelect = ZFFT_DETECT_SELECT;
 // starts of the runs of word `on`; below: the top bit of the word before (0 for the first)
 __device__ __forceinline__ u64 run_starts(u64 on, u64 below) { return on & ~((on << 1) | below); }
 
-template <int NW, int PER, int PL>
+// LOCAL (zfft_plan_detect_local): column j is on against its own floor, col_floor[row *
+// g.n_win + j] (detect_local_kernels.hip wrote it), instead of the row's; everything else,
+// the row's floor in floor_out included, is the same code.
+template <int NW, int PER, int PL, bool LOCAL>
 __global__ __launch_bounds__(64 * NW) void detect_rows_kernel(const float *__restrict__ rows, int64_t row_stride,
                                                               int count, DetectGeom g, float *__restrict__ floor_out,
                                                               int32_t *__restrict__ found_out,
                                                               zfft_emission *__restrict__ events,
-                                                              unsigned *__restrict__ occ) {
+                                                              unsigned *__restrict__ occ,
+                                                              const float *__restrict__ col_floor) {
   constexpr int WORDS = NW * PER, PR = PER - PL;  // per lane PR keys in registers, PL in LDS
   extern __shared__ uint32_t s_key[];  // [PL][64 NW]: a thread reads back only what it wrote
   __shared__ u64 s_on[WORDS], s_keep[WORDS];
@@ -188,14 +179,22 @@ __global__ __launch_bounds__(64 * NW) void detect_rows_kernel(const float *__res
     if (threadIdx.x == 0) floor_out[row] = floorv;
 
     // ---- on-flags
+    auto col_thr = [&](int i) -> float {
+      if constexpr (LOCAL) {  // past the row: the last column's floor, against a pad key (never on)
+        const int j = min((i * NW + wave) * 64 + lane, g.row_len - 1);
+        return __fadd_rn(col_floor[(int64_t)row * g.n_win + j], g.thr_add);  // a NaN floor: never on
+      } else {
+        return thr;
+      }
+    };
 #pragma unroll
     for (int i = 0; i < PR; ++i) {
-      const u64 on = __ballot(det_value(key[i]) >= thr);
+      const u64 on = __ballot(det_value(key[i]) >= col_thr(i));
       if (lane == 0) s_on[i * NW + wave] = s_keep[i * NW + wave] = on;
     }
 #pragma unroll 8
     for (int i = 0; i < PL; ++i) {
-      const u64 on = __ballot(det_value(s_key[i * (64 * NW) + threadIdx.x]) >= thr);
+      const u64 on = __ballot(det_value(s_key[i * (64 * NW) + threadIdx.x]) >= col_thr(PR + i));
       if (lane == 0) s_on[(PR + i) * NW + wave] = s_keep[(PR + i) * NW + wave] = on;
     }
     __syncthreads();
@@ -308,19 +307,20 @@ __global__ __launch_bounds__(64 * NW) void detect_rows_kernel(const float *__res
   }
 }
 
-template <int NW, int PER, int PL>
+template <int NW, int PER, int PL, bool LOCAL>
 hipError_t launch_form(const float *rows, int64_t row_stride, int count, const DetectGeom &g, int grid, float *floor_out,
-                       int32_t *found_out, zfft_emission *events, unsigned *occ, hipStream_t st) {
+                       int32_t *found_out, zfft_emission *events, unsigned *occ, const float *col_floor,
+                       hipStream_t st) {
   constexpr int lds = PL * 64 * NW * (int)sizeof(uint32_t);  // beside 21 KB of static LDS at most
   static bool attr_set = false;
   if (lds > 48 * 1024 && !attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)detect_rows_kernel<NW, PER, PL>,
+    hipError_t e = hipFuncSetAttribute((const void *)detect_rows_kernel<NW, PER, PL, LOCAL>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
-  hipLaunchKernelGGL((detect_rows_kernel<NW, PER, PL>), dim3((unsigned)grid), dim3(64 * NW), lds, st, rows, row_stride,
-                     count, g, floor_out, found_out, events, occ);
+  hipLaunchKernelGGL((detect_rows_kernel<NW, PER, PL, LOCAL>), dim3((unsigned)grid), dim3(64 * NW), lds, st, rows,
+                     row_stride, count, g, floor_out, found_out, events, occ, col_floor);
   return hipGetLastError();
 }
 
@@ -330,14 +330,18 @@ static_assert(sizeof(zfft_emission) == 16, "a record is one 16-byte store");
 
 hipError_t launch_detect_rows(const float *rows, int64_t row_stride, int count, const DetectGeom &g,
                               const DetectForm &f, float *floor_out, int32_t *found_out, zfft_emission *events,
-                              unsigned *occ, hipStream_t st) {
+                              unsigned *occ, hipStream_t st, const float *col_floor) {
   if (!f.ok() || count < 1 || f.grid < 1 || f.grid > count || g.row_len < 1 || g.row_len > f.cols() ||
       g.row_len > g.n_win || row_stride < g.row_len || g.max_per_row < 1 || g.max_per_row > kDetectMaxPerRow ||
       g.min_width < 1 || !(g.q >= 0.0 && g.q <= 1.0) || ((uintptr_t)events & 15))
     return hipErrorInvalidValue;
-#define ZFFT_DETECT_FORM(NW, PER, PL)   \
-  if (f.waves == NW && f.per == PER)    \
-    return launch_form<NW, PER, PL>(rows, row_stride, count, g, f.grid, floor_out, found_out, events, occ, st);
+  // (col_floor holds count rows of stride g.n_win, and row_len <= n_win: every read is inside)
+#define ZFFT_DETECT_FORM(NW, PER, PL)                                                                        \
+  if (f.waves == NW && f.per == PER)                                                                         \
+    return col_floor ? launch_form<NW, PER, PL, true>(rows, row_stride, count, g, f.grid, floor_out, found_out, \
+                                                      events, occ, col_floor, st)                             \
+                     : launch_form<NW, PER, PL, false>(rows, row_stride, count, g, f.grid, floor_out,        \
+                                                       found_out, events, occ, nullptr, st);
   ZFFT_DETECT_FORM(1, 1, 0)
   ZFFT_DETECT_FORM(1, 2, 0)
   ZFFT_DETECT_FORM(1, 4, 0)

@@ -415,7 +415,19 @@ struct DetectGeom {
 };
 hipError_t launch_detect_rows(const float *rows, int64_t row_stride, int count, const DetectGeom &g,
                               const DetectForm &form, float *floor_out, int32_t *found_out,
-                              zfft_emission *events, unsigned *occ, hipStream_t st);
+                              zfft_emission *events, unsigned *occ, hipStream_t st,
+                              const float *col_floor = nullptr);
+// col_floor (zfft_plan_detect_local): count rows of stride g.n_win; column j of row r is then on
+// against col_floor[r * g.n_win + j] + thr_add instead of the row's floor (which floor_out still
+// gets).
+// The local floors (zfft.h's rule of zfft_plan_detect_local; detect_local_kernels.hip):
+// floors[r * floor_stride + j], r < count, j < row_len, the value of rank floor(q (m - 1)) among
+// the m finite values of rows[r * row_stride + c], guard < |c - j| <= guard + half_window,
+// 0 <= c < row_len; NaN where m == 0.  Columns at or beyond row_len are left untouched.  `form`
+// is choose_detect_local's for these arguments.
+hipError_t launch_detect_floors(const float *rows, int64_t row_stride, int count, int row_len, int half_window,
+                                int guard, double q, const DetectLocalForm &form, float *floors, int64_t floor_stride,
+                                hipStream_t st);
 // Display viewport (zfft.h's rule; view_kernels.hip): one push of `count` rows of stride n_win
 // into the ring of H lines of `width` pixels, pixel x the columns [col0 + x span / width,
 // col0 + (x + 1) span / width).  The push continues a group of `pending` rows (its accumulator

@@ -123,6 +123,13 @@ struct zfft_plan {
   float dt_thr = 0.f;
   uint64_t dt_rows = 0;
   DevBuf dt_occ, dt_stage, dt_out;
+  // the local floor (zfft_plan_detect_local): dt_h = half_window, 0 = the row-global floor (no
+  // buffer).  dt_floors holds the floors of a pass, at most dt_local_cap bytes (0 = the default,
+  // kDetectLocalScratch; test hook zfft__plan_detect_local_cap)
+  int dt_h = 0, dt_guard = 0;
+  size_t dt_local_cap = 0;
+  int dt_row_len = 0;  // test hook zfft__plan_detect_row_length: the detector's row length (0 = the plan's)
+  DevBuf dt_floors;
   // display viewport (zfft_plan_viewport; zfft_viewport.cpp): vw_h = 0 is off (no buffer).  A
   // ring of vw_h lines of vw_w pixels in the waterfall ring's convention (vw_off, vw_scroll),
   // the traces last / max_hold / min_hold (3 x vw_w floats), the pending group's accumulator

@@ -465,6 +465,51 @@ class ZoomFFT:
         check(self.lib.zfft_plan_detect(self._plan, float(quantile), float(threshold_db), int(min_width),
                                         int(max_per_row)), "zfft_plan_detect")
 
+    def set_detect_local(self, half_window: int, guard: int = 0) -> None:
+        """A local noise floor per column (zfft_plan_detect_local; order-statistic CFAR): column j
+        is judged against the rank-floor(quantile (m - 1)) value of the finite rows' values in the
+        `half_window` (1..128) columns beyond `guard` (0..128) columns on either side of it, cut
+        at the row's ends, instead of the row's one floor.  half_window = 0 is the row-global
+        floor again.  Detection must be on; zeroes the occupancy.  `detect` and `detect_device`
+        follow the mode; the per-row `floor` they return stays the row-global one."""
+        check(self.lib.zfft_plan_detect_local(self._plan, int(half_window), int(guard)), "zfft_plan_detect_local")
+
+    def detect_local_shape(self):
+        """(half_window, guard); (0, 0) with the row-global floor."""
+        h, g = ctypes.c_int32(), ctypes.c_int32()
+        check(self.lib.zfft_detect_local_shape(self._plan, ctypes.byref(h), ctypes.byref(g)),
+              "zfft_detect_local_shape")
+        return h.value, g.value
+
+    def _detect_rows_arg(self, rows):
+        """Host rows as contiguous float32 (count, n_win); row_length-wide rows get a NaN tail."""
+        r = np.asarray(rows, dtype=np.float32)
+        r = r.reshape(-1, r.shape[-1])
+        if r.shape[1] != self.n_win:
+            if r.shape[1] != self.row_length:
+                raise ValueError("rows must be n_win or row_length wide")
+            full = np.full((r.shape[0], self.n_win), np.nan, dtype=np.float32)  # the tail is never read
+            full[:, :r.shape[1]] = r
+            r = full
+        return np.ascontiguousarray(r)
+
+    def detect_floors(self, rows) -> np.ndarray:
+        """float32 (count, n_win): the local floor of every column of host rows (as `detect`
+        takes them), NaN where a column has no finite reference cell and at or beyond
+        row_length; local mode only; synchronous.  No occupancy, no rows_seen."""
+        r = self._detect_rows_arg(rows)
+        out = np.empty_like(r)
+        check(self.lib.zfft_detect_floors(self._plan, r.ctypes.data_as(ctypes.c_void_p), r.shape[0],
+                                          out.ctypes.data_as(ctypes.c_void_p)), "zfft_detect_floors")
+        return out
+
+    def detect_floors_device(self, d_rows_ptr: int, count: int, d_floors_ptr: int, stream: int = 0) -> None:
+        """`count` device rows of n_win floats into device floors of the same shape (columns at
+        or beyond row_length are left untouched); enqueued on `stream`, no sync."""
+        check(self.lib.zfft_detect_floors_device(self._plan, ctypes.c_void_p(d_rows_ptr), int(count),
+                                                 ctypes.c_void_p(d_floors_ptr), ctypes.c_void_p(stream or None)),
+              "zfft_detect_floors_device")
+
     def detect_shape(self):
         """(max_per_row, n_win)."""
         k, w = ctypes.c_int32(), ctypes.c_int32()
@@ -476,15 +521,7 @@ class ZoomFFT:
         (floor float32[count], found int32[count], events), events a structured array of shape
         (count, max_per_row) with fields first, last, peak, peak_db; synchronous."""
         K = self.detect_shape()[0]
-        r = np.asarray(rows, dtype=np.float32)
-        r = r.reshape(-1, r.shape[-1])
-        if r.shape[1] != self.n_win:
-            if r.shape[1] != self.row_length:
-                raise ValueError("rows must be n_win or row_length wide")
-            full = np.full((r.shape[0], self.n_win), np.nan, dtype=np.float32)  # the tail is never read
-            full[:, :r.shape[1]] = r
-            r = full
-        r = np.ascontiguousarray(r)
+        r = self._detect_rows_arg(rows)
         count = r.shape[0]
         floor = np.empty(count, dtype=np.float32)
         found = np.empty(count, dtype=np.int32)

@@ -335,12 +335,17 @@ class Detector:
 
     `update` takes one row or (R, W) rows and lazily builds a plan for their width, like
     `Persistence`; a new width rebuilds it and starts from zeros.  `events` is (R, max_per_row)
-    with fields first, last, peak, peak_db; `frequencies` maps its columns to Hz."""
+    with fields first, last, peak, peak_db; `frequencies` maps its columns to Hz.
+
+    `local=(half_window, guard)` judges every column against a floor of its own, the `quantile`
+    of the half_window columns beyond `guard` columns on either side (order-statistic CFAR,
+    ZoomFFT.set_detect_local): for rows whose floor is not flat.  `floors` gives those floors."""
 
     def __init__(self, quantile: float = 0.5, threshold_db: float = 12.0, min_width: int = 1,
-                 max_per_row: int = 8, device: int = 0, fs: float = 2.4e6):
+                 max_per_row: int = 8, device: int = 0, fs: float = 2.4e6, local=None):
         self.quantile, self.threshold_db = float(quantile), float(threshold_db)
         self.min_width, self.max_per_row = int(min_width), int(max_per_row)
+        self.local = None if local is None else (int(local[0]), int(local[1]))
         self.device = device
         self.fs = fs
         self.width = 0
@@ -353,6 +358,8 @@ class Detector:
             n_fft = 1 << max(5, (n_win - 1).bit_length())
             self._plan = ZoomFFT(n_fft, 1, self.fs, n_win=n_win, device=self.device)
             self._plan.set_detect(self.quantile, self.threshold_db, self.min_width, self.max_per_row)
+            if self.local is not None:
+                self._plan.set_detect_local(*self.local)
             self.width = width
 
     def _need_plan(self):
@@ -366,15 +373,25 @@ class Detector:
             self._plan = None
             self.width = 0
 
-    def update(self, psd_rows):
-        """(floor float32[R], found int32[R], events[R, max_per_row]) of the rows."""
+    def _rows(self, psd_rows):
         rows = np.asarray(psd_rows, dtype=np.float32)
         rows = rows.reshape(-1, rows.shape[-1])
         width = rows.shape[1]
         self._ensure(width)
         if self._plan.n_win != width:
             rows = np.concatenate([rows, np.full((len(rows), 1), np.nan, np.float32)], axis=1)
+        return rows
+
+    def update(self, psd_rows):
+        """(floor float32[R], found int32[R], events[R, max_per_row]) of the rows."""
+        rows = self._rows(psd_rows)  # (builds the plan)
         return self._plan.detect(rows)
+
+    def floors(self, psd_rows) -> np.ndarray:
+        """float32 (R, W): the local floor of every column of the rows (`local` detectors only);
+        counts nothing."""
+        rows = self._rows(psd_rows)
+        return self._plan.detect_floors(rows)[:, :self.width]
 
     @property
     def rows_seen(self) -> int:
