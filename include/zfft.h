@@ -482,6 +482,94 @@ int zfft_detect_local_shape(const zfft_plan *plan, int32_t *half_window, int32_t
 int zfft_detect_floors_device(zfft_plan *plan, const float *d_rows, int32_t count, float *d_floors, void *hip_stream);
 int zfft_detect_floors(zfft_plan *plan, const float *rows, int32_t count, float *floors_out);
 
+/* Emission tracks: the detector's runs linked across rows on the device, so that a carrier that
+ * stays, a burst, a chirp are one record each -- when it began and ended, the band it covered,
+ * where and how strong its peak was -- instead of one record per row.  In the model of the
+ * detector it belongs to: nothing runs inside zfft_process*, the caller hands over the very
+ * buffers zfft_detect_device wrote, and a plan that never enables it allocates and launches
+ * nothing for it.  The rule (integers throughout, reproducible bit for bit in numpy;
+ * tests/track_ref.py):
+ *   Rows given to the tracker are numbered t = 0, 1, 2, ... from the last reset (64-bit; the
+ *   kernels hold row * 32 + slot in 64 bits, so t < 2^58).
+ *   1. nodes: row t contributes its recorded runs, the slots s = 0 .. min(max(found, 0), K) - 1
+ *      of the detector's output for that row, K the plan's max_per_row; each a record (first,
+ *      last, peak, peak_db) as rules 4-6 of zfft_plan_detect define it.  A row with found > K
+ *      counts once in truncated_rows; its runs beyond K do not exist for the tracker.
+ *   2. links: runs a (row t_a) and b (row t_b) with 1 <= t_b - t_a <= gap + 1 are linked when
+ *      first_a <= last_b + slack && first_b <= last_a + slack.  gap in [0, 7]: the rows an
+ *      emission may be absent for (keying, fading); slack in [0, 64]: 0 means the two runs share
+ *      a column, 1 that they may merely touch.  The rows in between do not matter; runs of one
+ *      row are never linked to each other.
+ *   3. a track is a connected component of that graph.  Its record, zfft_track: row_first,
+ *      row_last the lowest and highest row of its runs; cells the sum of last - first + 1 and
+ *      runs the number of its runs; col_first = min first, col_last = max last; slot_first the
+ *      lowest slot among its runs in row_first; peak_db the maximum of its runs' peak_db as a
+ *      float comparison (-0.0 and 0.0 are equal; a zero maximum is reported as 0.0);
+ *      (peak_row, peak_col) the lexicographically lowest (row, peak) among the runs that hold
+ *      that maximum; reserved = 0.  (row_first, slot_first) names a track uniquely.
+ *   4. closing: after S rows have been given a track is closed when row_last + gap + 1 < S -- no
+ *      later row can reach it -- and open otherwise.  A closed track with row_last - row_first
+ *      + 1 >= min_rows (min_rows >= 1) is reported; any other closed track counts in
+ *      short_tracks and is forgotten.
+ *   5. order: zfft_track_read returns the reported tracks not yet read in ascending (row_last,
+ *      row_first, slot_first) and removes them from the store.  The closed set after S rows is
+ *      {row_last <= S - gap - 2}, so the sequence over all reads is the same however the rows
+ *      were cut into calls and however the reads were interleaved with them.
+ *   6. store: at most max_tracks (1 .. 2^22) reported tracks wait unread; one that finds the
+ *      store full counts in dropped and is lost (which ones are lost is not defined).  With
+ *      dropped == 0 every output is exactly this rule.
+ *   7. flush: zfft_track_flush closes every open track as it stands, reporting or counting it by
+ *      min_rows, in the order of rule 5 among themselves.  The row counter does not advance;
+ *      later rows link to nothing earlier.
+ *   8. open tracks: zfft_track_open copies the open tracks as they stand now, in ascending
+ *      (row_first, slot_first), and changes nothing.  There are at most (gap + 1) * K of them;
+ *      an endless carrier never closes, and this call is how a display sees it.
+ *   9. input: records as the detector writes them -- ascending, disjoint, 0 <= first <= peak <=
+ *      last, peak_db not NaN.  The host form checks the slots it will use and returns
+ *      ZFFT_EINVAL otherwise; in the device form other contents give undefined track values.
+ *      Columns are only ever compared, never used as addresses: the kernels stay in bounds
+ *      whatever the records hold.  found < 0 is 0 and found > K is K, as in rule 1.
+ * Tracking belongs to the detector and needs detection on (K is the detector's):
+ * zfft_plan_detect(..., max_per_row = 0) switches it off and frees it, and a zfft_plan_detect call
+ * that changes max_per_row while tracking is on resets the tracker.  Every zfft_track_* call on a
+ * plan with tracking off returns ZFFT_EINVAL (zfft_track_shape after reporting max_tracks 0).
+ * zfft_track_push_device is enqueued on its stream with no sync, ordered after earlier work on
+ * that stream and after the plan's earlier calls on any stream; read, open, state and flush wait
+ * for what is enqueued.  With zfft_plan_timing on a push reports its launches by name
+ * ("track_label", "track_seam", ...: zfft_plan_timings then describes that push). */
+typedef struct zfft_track {
+  int64_t row_first, row_last; /* lowest and highest row of its runs */
+  int64_t peak_row;
+  uint64_t cells; /* sum of last - first + 1 over its runs */
+  uint64_t runs;  /* number of runs */
+  int32_t col_first, col_last; /* min first, max last */
+  int32_t peak_col;
+  int32_t slot_first; /* lowest slot among its runs in row_first */
+  float peak_db;      /* max peak_db, as a float comparison */
+  int32_t reserved;   /* 0 */
+} zfft_track; /* 64 bytes */
+typedef struct zfft_track_stats {
+  uint64_t rows_seen, open, unread, dropped, short_tracks, truncated_rows;
+} zfft_track_stats;
+/* max_tracks = 0: off, frees everything.  Otherwise gap in [0, 7], slack in [0, 64], min_rows >= 1,
+ * max_tracks in [1, 2^22]; anything else, or detection off, ZFFT_EINVAL.  A call resets the tracker. */
+int zfft_plan_track(zfft_plan *plan, int32_t gap, int32_t slack, int32_t min_rows, int32_t max_tracks);
+int zfft_track_shape(const zfft_plan *plan, int32_t *gap, int32_t *slack, int32_t *min_rows, int32_t *max_tracks);
+/* count rows' found (count int32) and records (count * max_per_row) on the device, 1 <= count <= 2^26;
+ * `stream` is a hipStream_t like every hip_stream of this header (its ordering case, behind a
+ * stalled stream, is in tests/test_gpu_track.py) */
+int zfft_track_push_device(zfft_plan *plan, const int32_t *d_found, const zfft_emission *d_events, int32_t count,
+                           void *stream);
+/* host found and records, checked by rule 9; synchronous */
+int zfft_track_push(zfft_plan *plan, const int32_t *found, const zfft_emission *events, int32_t count);
+/* at most `max` reported tracks into out, *n their number; removes them from the store */
+int zfft_track_read(zfft_plan *plan, zfft_track *out, int32_t max, int32_t *n);
+/* at most `max` open tracks into out, *n their number; changes nothing */
+int zfft_track_open(zfft_plan *plan, zfft_track *out, int32_t max, int32_t *n);
+int zfft_track_flush(zfft_plan *plan);
+int zfft_track_state(zfft_plan *plan, zfft_track_stats *out);
+int zfft_track_reset(zfft_plan *plan); /* everything back to zero, the store emptied */
+
 /* Display viewport: a second, display-sized image kept on the device, reduced from the rows the
  * caller pushes as a spectrum analyser's display detector does -- every pixel the max, min or
  * mean of all the columns and rows that fall into it -- in the model of the ring, persistence

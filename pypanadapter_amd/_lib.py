@@ -84,6 +84,8 @@ EXPORTS = [
     "zfft_plan_detect", "zfft_detect_shape", "zfft_detect_device", "zfft_detect", "zfft_detect_occupancy",
     "zfft_detect_reset",
     "zfft_plan_detect_local", "zfft_detect_local_shape", "zfft_detect_floors_device", "zfft_detect_floors",
+    "zfft_plan_track", "zfft_track_shape", "zfft_track_push_device", "zfft_track_push", "zfft_track_read",
+    "zfft_track_open", "zfft_track_flush", "zfft_track_state", "zfft_track_reset",
     "zfft_plan_viewport", "zfft_viewport_edge", "zfft_viewport_shape", "zfft_viewport_push_device",
     "zfft_viewport_push", "zfft_viewport_state", "zfft_viewport_read", "zfft_viewport_traces",
     "zfft_viewport_hold_reset", "zfft_viewport_reset", "zfft_viewport_render_device", "zfft_viewport_render",
@@ -188,6 +190,15 @@ def load(path: str = ""):
         "zfft_detect_local_shape": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
         "zfft_detect_floors_device": (ctypes.c_int, [P, P, I32, P, P]),
         "zfft_detect_floors": (ctypes.c_int, [P, P, I32, P]),
+        "zfft_plan_track": (ctypes.c_int, [P, I32, I32, I32, I32]),
+        "zfft_track_shape": (ctypes.c_int, [P] + [ctypes.POINTER(I32)] * 4),
+        "zfft_track_push_device": (ctypes.c_int, [P, P, P, I32, P]),
+        "zfft_track_push": (ctypes.c_int, [P, P, P, I32]),
+        "zfft_track_read": (ctypes.c_int, [P, P, I32, ctypes.POINTER(I32)]),
+        "zfft_track_open": (ctypes.c_int, [P, P, I32, ctypes.POINTER(I32)]),
+        "zfft_track_flush": (ctypes.c_int, [P]),
+        "zfft_track_state": (ctypes.c_int, [P, P]),
+        "zfft_track_reset": (ctypes.c_int, [P]),
         "zfft_plan_viewport": (ctypes.c_int, [P, I32, I32, I32, I32, I32, I32]),
         "zfft_viewport_edge": (I64, [I32, I32, I32, I32]),
         "zfft_viewport_shape": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),

@@ -107,6 +107,7 @@ int zfft_plan_detect(zfft_plan *p, double quantile, double threshold_db, int32_t
     p->dt_stage.release();
     p->dt_out.release();
     p->dt_floors.release();
+    track_release(p);  // tracking belongs to the detector
     p->dt_k = 0;
     p->dt_rows = 0;
     p->dt_h = p->dt_guard = 0;  // the next zfft_plan_detect starts row-global
@@ -120,11 +121,14 @@ int zfft_plan_detect(zfft_plan *p, double quantile, double threshold_db, int32_t
     p->dt_k = 0;
     return fail(ZFFT_ENOMEM, "detect occupancy allocation failed");
   }
+  const bool new_k = p->dt_k != max_per_row;
   p->dt_k = max_per_row;
   p->dt_q = quantile;
   p->dt_thr = (float)threshold_db;
   p->dt_min_width = min_width;
-  return zero_occupancy(p);
+  rc = zero_occupancy(p);
+  if (rc || !new_k) return rc;
+  return track_restart(p);  // the tracker's rows had another K (nothing to do while it is off)
 }
 
 int zfft_plan_detect_local(zfft_plan *p, int32_t half_window, int32_t guard) {

@@ -12,6 +12,7 @@
 
 #include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
 #include "zfft_history_plan.h"  // the row history's quantiser and forms (HistQuant, HistForm)
+#include "zfft_track_plan.h"   // the emission tracker's forms and carried records (TrackForm, TrackOpen)
 #include "zfft_view_plan.h"    // the viewport's forms (ViewForm)
 #include "zfft_welch_plan.h"  // the Welch forms' domains (kMaxLdsFft, kDifMin / kDifMax, ...), WelchSel
 
@@ -428,6 +429,38 @@ hipError_t launch_detect_rows(const float *rows, int64_t row_stride, int count, 
 hipError_t launch_detect_floors(const float *rows, int64_t row_stride, int count, int row_len, int half_window,
                                 int guard, double q, const DetectLocalForm &form, float *floors, int64_t floor_stride,
                                 hipStream_t st);
+// Emission tracker (zfft.h's rule of zfft_plan_track; track_kernels.hip): one pass of R rows,
+// found / events the pass's first row's, t0 its row number.  The carried state (fr_*: the last
+// G = gap + 1 rows given, row-major, K slots each; open_tab; ctr; store, a ring read from `head`)
+// and the pass's scratch (per node of the (R + G) * K: parent, the candidates c_* and the aggregates
+// a_*, these zeroed before the first step; per local row: rowcnt, rowoff).  The steps 0 .. kTrackSteps - 1 run in
+// order on one stream; kTrackStepNames[step] is the launch's name.
+struct TrackArgs {
+  int K, G, slack, min_rows, max_tracks;
+  int R, chunk_rows, chunks;
+  int64_t t0;
+  uint32_t head;
+  const int32_t *found;
+  const zfft_emission *events;
+  zfft_emission *fr_ev;
+  int32_t *fr_found;
+  uint32_t *fr_parent;
+  TrackOpen *open_tab;
+  TrackCounters *ctr;
+  zfft_track *store;
+  uint32_t *parent;
+  uint64_t *a_name, *a_last, *a_cells, *a_runs, *a_prow;
+  uint32_t *a_colf, *a_coll, *a_pkey, *a_pcol;
+  // per candidate (a chunk's root, a seeded frontier node): the peak of its part, plain values
+  uint64_t *c_prow;
+  uint32_t *c_pkey, *c_pcol;
+  int32_t *rowcnt, *rowoff;  // per local row its reported tracks; per kTrackThreads rows their store offset
+};
+constexpr int kTrackSteps = 9;
+extern const char *const kTrackStepNames[kTrackSteps];
+hipError_t launch_track_step(int step, const TrackArgs &a, hipStream_t st);
+// Closes every open track as it stands and empties the frontier (needs the carried state only).
+hipError_t launch_track_flush(const TrackArgs &a, hipStream_t st);
 // Display viewport (zfft.h's rule; view_kernels.hip): one push of `count` rows of stride n_win
 // into the ring of H lines of `width` pixels, pixel x the columns [col0 + x span / width,
 // col0 + (x + 1) span / width).  The push continues a group of `pending` rows (its accumulator

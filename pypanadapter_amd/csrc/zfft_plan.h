@@ -1,6 +1,6 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
-// zfft_detect.cpp, zfft_viewport.cpp, zfft_history.cpp).  Not part of the C-ABI.
+// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -130,6 +130,15 @@ struct zfft_plan {
   size_t dt_local_cap = 0;
   int dt_row_len = 0;  // test hook zfft__plan_detect_row_length: the detector's row length (0 = the plan's)
   DevBuf dt_floors;
+  // emission tracker (zfft_plan_track; zfft_track.cpp): tk_max = max_tracks, 0 = off (no buffer).
+  // tk_state holds the carried state (frontier, open table, counters), tk_store the ring of
+  // tk_max records read from tk_head, tk_scratch a pass's union-find and aggregates, tk_stage the
+  // device staging of zfft_track_push's host records.  tk_rows counts the rows given (host side:
+  // pushes are in call order)
+  int tk_max = 0, tk_gap = 0, tk_slack = 0, tk_min_rows = 1;
+  uint64_t tk_rows = 0;
+  uint32_t tk_head = 0;
+  DevBuf tk_state, tk_store, tk_scratch, tk_stage;
   // display viewport (zfft_plan_viewport; zfft_viewport.cpp): vw_h = 0 is off (no buffer).  A
   // ring of vw_h lines of vw_w pixels in the waterfall ring's convention (vw_off, vw_scroll),
   // the traces last / max_hold / min_hold (3 x vw_w floats), the pending group's accumulator
@@ -211,6 +220,12 @@ int ensure_lo(zfft_plan *p, int64_t L);
 // schedule choose_schedule gives; *out = the decimated frames, natural layout.
 int run_decimator(zfft_plan *p, const InDesc &in, int64_t L, int frames,
                   const std::vector<int64_t> &n, const float2 **out, hipStream_t st);
+
+// --- zfft_track.cpp ---
+// Frees the emission tracker and switches it off (the caller has waited for the plan's work).
+void track_release(zfft_plan *p);
+// Everything of the tracker back to zero, in stream order; nothing while it is off.
+int track_restart(zfft_plan *p);
 
 // --- zfft_welch.cpp ---
 // The Welch rows (or lines) of `frames` decimated frames of Ld samples at x into d_rows, by the

@@ -553,6 +553,71 @@ class ZoomFFT:
     def detect_reset(self) -> None:
         check(self.lib.zfft_detect_reset(self._plan), "zfft_detect_reset")
 
+    # ---------------------------------------------------------------- emission tracks
+    def set_track(self, gap: int = 0, slack: int = 0, min_rows: int = 1, max_tracks: int = 65536) -> None:
+        """The emission tracker (zfft_plan_track): the detector's runs linked across rows on the
+        device.  Runs at most `gap` + 1 rows apart (gap in [0, 7]) whose column ranges come
+        within `slack` of each other (0: they share a column; at most 64) belong to one track; a
+        track that no later row can reach is closed, reported when it spans at least `min_rows`
+        rows and counted in `short_tracks` otherwise; at most `max_tracks` reported tracks wait
+        for `tracks()`.  Detection must be on; max_tracks = 0 turns tracking off.  Resets the
+        tracker.  The rule is in include/zfft.h, bit for bit reproducible in numpy."""
+        check(self.lib.zfft_plan_track(self._plan, int(gap), int(slack), int(min_rows), int(max_tracks)),
+              "zfft_plan_track")
+
+    def track_shape(self):
+        """(gap, slack, min_rows, max_tracks)."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        check(self.lib.zfft_track_shape(self._plan, *[ctypes.byref(x) for x in v]), "zfft_track_shape")
+        return tuple(x.value for x in v)
+
+    def track_push(self, found, events) -> None:
+        """The next rows' `found` (count int32) and `events` (count, max_per_row) as `detect`
+        returned them, from the host; the records are checked against the detector's contract.
+        Synchronous."""
+        K = self.detect_shape()[0]
+        f = np.ascontiguousarray(np.atleast_1d(found), dtype=np.int32)
+        e = np.ascontiguousarray(events, dtype=EMISSION_DTYPE).reshape(-1, K)
+        if f.ndim != 1 or e.shape[0] != f.shape[0]:
+            raise ValueError(f"found must be (count,) and events (count, {K})")
+        check(self.lib.zfft_track_push(self._plan, f.ctypes.data_as(ctypes.c_void_p),
+                                       e.ctypes.data_as(ctypes.c_void_p), f.shape[0]), "zfft_track_push")
+
+    def track_push_device(self, d_found_ptr: int, d_events_ptr: int, count: int, stream: int = 0) -> None:
+        """The buffers `detect_device` wrote for `count` rows; enqueued on `stream`, no sync."""
+        check(self.lib.zfft_track_push_device(self._plan, ctypes.c_void_p(d_found_ptr), ctypes.c_void_p(d_events_ptr),
+                                              int(count), ctypes.c_void_p(stream or None)), "zfft_track_push_device")
+
+    def _track_records(self, fn, name, max):
+        out = np.empty(max, dtype=TRACK_DTYPE)
+        n = ctypes.c_int32()
+        check(fn(self._plan, out.ctypes.data_as(ctypes.c_void_p), int(max), ctypes.byref(n)), name)
+        return out[:n.value].copy()
+
+    def tracks(self, max: int | None = None) -> np.ndarray:
+        """The reported tracks not yet read (at most `max`), in ascending (row_last, row_first,
+        slot_first), as a TRACK_DTYPE array; they leave the store.  Waits for enqueued pushes."""
+        if max is None:
+            max = self.track_state()["unread"]
+        return self._track_records(self.lib.zfft_track_read, "zfft_track_read", max)
+
+    def open_tracks(self) -> np.ndarray:
+        """The tracks still open, as they stand now, in ascending (row_first, slot_first)."""
+        return self._track_records(self.lib.zfft_track_open, "zfft_track_open", 256)
+
+    def track_flush(self) -> None:
+        """Close every open track as it stands; later rows link to nothing earlier."""
+        check(self.lib.zfft_track_flush(self._plan), "zfft_track_flush")
+
+    def track_state(self) -> dict:
+        """rows_seen, open, unread, dropped, short_tracks, truncated_rows."""
+        v = (ctypes.c_uint64 * 6)()
+        check(self.lib.zfft_track_state(self._plan, ctypes.cast(v, ctypes.c_void_p)), "zfft_track_state")
+        return dict(zip(("rows_seen", "open", "unread", "dropped", "short_tracks", "truncated_rows"), map(int, v)))
+
+    def track_reset(self) -> None:
+        check(self.lib.zfft_track_reset(self._plan), "zfft_track_reset")
+
     # ---------------------------------------------------------------- display viewport
     def set_viewport(self, height: int, width: int, col0: int = 0, col1: int | None = None,
                      detector: str = "max", rows_per_line: int = 1) -> None:
@@ -775,6 +840,11 @@ class ZoomFFT:
 
 # zfft_emission (include/zfft.h): one record of ZoomFFT.detect
 EMISSION_DTYPE = np.dtype([("first", np.int32), ("last", np.int32), ("peak", np.int32), ("peak_db", np.float32)])
+# zfft_track (include/zfft.h): one record of ZoomFFT.tracks / open_tracks
+TRACK_DTYPE = np.dtype([("row_first", np.int64), ("row_last", np.int64), ("peak_row", np.int64),
+                        ("cells", np.uint64), ("runs", np.uint64), ("col_first", np.int32),
+                        ("col_last", np.int32), ("peak_col", np.int32), ("slot_first", np.int32),
+                        ("peak_db", np.float32), ("reserved", np.int32)])
 
 
 _IN_DTYPES = {"complex64": (0, np.complex64, 1), "complex32": (1, np.float16, 2),

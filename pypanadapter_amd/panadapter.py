@@ -339,10 +339,18 @@ class Detector:
 
     `local=(half_window, guard)` judges every column against a floor of its own, the `quantile`
     of the half_window columns beyond `guard` columns on either side (order-statistic CFAR,
-    ZoomFFT.set_detect_local): for rows whose floor is not flat.  `floors` gives those floors."""
+    ZoomFFT.set_detect_local): for rows whose floor is not flat.  `floors` gives those floors.
+
+    `track=(gap, slack, min_rows)` links what `update` detects across rows on the device
+    (ZoomFFT.set_track): `tracks()` returns the emissions that have ended since the last call --
+    first and last row, the band, the peak -- and `open_tracks()` those still on the air;
+    `track_extent` maps them to seconds and Hz."""
 
     def __init__(self, quantile: float = 0.5, threshold_db: float = 12.0, min_width: int = 1,
-                 max_per_row: int = 8, device: int = 0, fs: float = 2.4e6, local=None):
+                 max_per_row: int = 8, device: int = 0, fs: float = 2.4e6, local=None, track=None,
+                 max_tracks: int = 65536):
+        self.track = None if track is None else tuple(int(v) for v in track)
+        self.max_tracks = int(max_tracks)
         self.quantile, self.threshold_db = float(quantile), float(threshold_db)
         self.min_width, self.max_per_row = int(min_width), int(max_per_row)
         self.local = None if local is None else (int(local[0]), int(local[1]))
@@ -360,6 +368,8 @@ class Detector:
             self._plan.set_detect(self.quantile, self.threshold_db, self.min_width, self.max_per_row)
             if self.local is not None:
                 self._plan.set_detect_local(*self.local)
+            if self.track is not None:
+                self._plan.set_track(*self.track, max_tracks=self.max_tracks)
             self.width = width
 
     def _need_plan(self):
@@ -385,7 +395,29 @@ class Detector:
     def update(self, psd_rows):
         """(floor float32[R], found int32[R], events[R, max_per_row]) of the rows."""
         rows = self._rows(psd_rows)  # (builds the plan)
-        return self._plan.detect(rows)
+        out = self._plan.detect(rows)
+        if self.track is not None:
+            self._plan.track_push(out[1], out[2])
+        return out
+
+    def tracks(self, max: int | None = None) -> np.ndarray:
+        """The emissions that ended since the last call (ZoomFFT.tracks; `track=` detectors only)."""
+        return self._need_plan().tracks(max)
+
+    def open_tracks(self) -> np.ndarray:
+        """The emissions still open: a carrier that never ends is only ever seen here."""
+        return self._need_plan().open_tracks()
+
+    def track_extent(self, tracks, fs: float, n_fft: int, zoom: int, line_period: float) -> dict:
+        """Where the tracks lie in time and frequency: t_start, t_end (seconds; a row lasts
+        `line_period` and row r covers [r, r + 1) periods), f_lo, f_hi and f_peak (Hz from the
+        centre, the column centres as `frequencies` gives them), t_peak, peak_db."""
+        f = self.frequencies(fs, n_fft, zoom)
+        t = np.asarray(tracks)
+        ok = lambda c: np.clip(c, 0, self.width - 1)  # (the NaN column of an odd width is never on)
+        return dict(t_start=t["row_first"] * float(line_period), t_end=(t["row_last"] + 1) * float(line_period),
+                    f_lo=f[ok(t["col_first"])], f_hi=f[ok(t["col_last"])], f_peak=f[ok(t["peak_col"])],
+                    t_peak=t["peak_row"] * float(line_period), peak_db=t["peak_db"].copy())
 
     def floors(self, psd_rows) -> np.ndarray:
         """float32 (R, W): the local floor of every column of the rows (`local` detectors only);
