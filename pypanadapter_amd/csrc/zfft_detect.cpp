@@ -18,8 +18,6 @@ using namespace zfft;
 
 namespace {
 
-constexpr int32_t kMaxCount = 1 << 26;  // rows per call (count * max_per_row records stay below 2^31)
-
 // The detector's rows are the plan's (zfft_plan_row_length) unless the test hook gave a length.
 int det_length(const zfft_plan *p) { return p->dt_row_len ? p->dt_row_len : row_length(p); }
 
@@ -104,7 +102,7 @@ int zfft_plan_detect(zfft_plan *p, double quantile, double threshold_db, int32_t
     rc = quiesce(p);  // an enqueued call may still add to the table and read the staging
     if (rc) return rc;
     p->dt_occ.release();
-    p->dt_stage.release();
+    p->row_stage.release();
     p->dt_out.release();
     p->dt_floors.release();
     track_release(p);  // tracking belongs to the detector
@@ -170,7 +168,7 @@ int zfft_detect_device(zfft_plan *p, const float *d_rows, int32_t count, float *
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!d_rows || !d_floor || !d_found || !d_events || count < 1 || count > kMaxCount)
+  if (!d_rows || !d_floor || !d_found || !d_events || count < 1 || count > kMaxDetectRows)
     return fail(ZFFT_EINVAL, "bad rows / outputs / count");
   if ((uintptr_t)d_events & 15) return fail(ZFFT_EINVAL, "detect: the records must be 16-byte aligned");
   const DetectGeom g{p->cfg.n_win, det_length(p), p->dt_q, p->dt_thr, p->dt_min_width, p->dt_k};
@@ -182,12 +180,8 @@ int zfft_detect_device(zfft_plan *p, const float *d_rows, int32_t count, float *
     const DetectLocalForm lf = choose_detect_local(g.row_len, n_win, count, p->dt_h, p->dt_guard, p->dt_local_cap);
     if (!lf.ok()) return fail(ZFFT_EINVAL, "detect: no local form for this plan");
     const size_t need = (size_t)lf.chunk_rows * n_win * sizeof(float);
-    if (p->dt_floors.cap < need) {
-      rc = quiesce(p);  // growing frees what an earlier call may still read
-      if (rc) return rc;
-      if (p->dt_floors.ensure(need) != hipSuccess) return fail(ZFFT_ENOMEM, "detect floors allocation failed");
-    }
-    rc = use_stream(p, st);
+    rc = grow(p, p->dt_floors, need, "detect floors");
+    if (!rc) rc = use_stream(p, st);
     if (rc) return rc;
     p->dt_rows += (uint64_t)count;
     p->n_marks = 0;
@@ -224,31 +218,22 @@ int zfft_detect(zfft_plan *p, const float *rows, int32_t count, float *floor_out
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!rows || !floor_out || !found_out || !events_out || count < 1 || count > kMaxCount)
+  if (!rows || !floor_out || !found_out || !events_out || count < 1 || count > kMaxDetectRows)
     return fail(ZFFT_EINVAL, "bad rows / outputs / count");
-  const size_t in_bytes = (size_t)count * p->cfg.n_win * sizeof(float);
   // the records first (16-byte aligned), then the floors, then the counts
   const size_t ev_bytes = (size_t)count * p->dt_k * sizeof(zfft_emission), n4 = (size_t)count * 4;
-  if (p->dt_stage.cap < in_bytes || p->dt_out.cap < ev_bytes + 2 * n4) {
-    rc = quiesce(p);  // growing frees what an earlier call may still use
-    if (rc) return rc;
-    if (p->dt_stage.ensure(in_bytes) != hipSuccess || p->dt_out.ensure(ev_bytes + 2 * n4) != hipSuccess)
-      return fail(ZFFT_ENOMEM, "detect staging allocation failed");
-  }
-  rc = use_stream(p, p->stream);  // the staging may still be read by the previous call
+  const float *d_rows;
+  rc = grow(p, p->dt_out, ev_bytes + 2 * n4, "detect staging");
+  if (!rc) rc = stage_rows(p, rows, count, "detect staging", &d_rows);
   if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(p->dt_stage.p, rows, in_bytes, hipMemcpyHostToDevice, p->stream);
-  if (e != hipSuccess) return hip_fail(e, "H2D rows");
   char *out = p->dt_out.as<char>();
-  rc = zfft_detect_device(p, p->dt_stage.as<float>(), count, (float *)(out + ev_bytes),
-                          (int32_t *)(out + ev_bytes + n4), (zfft_emission *)out, p->stream);
+  rc = zfft_detect_device(p, d_rows, count, (float *)(out + ev_bytes), (int32_t *)(out + ev_bytes + n4),
+                          (zfft_emission *)out, p->stream);
   if (rc) return rc;
-  e = hipMemcpyAsync(events_out, out, ev_bytes, hipMemcpyDeviceToHost, p->stream);
+  hipError_t e = hipMemcpyAsync(events_out, out, ev_bytes, hipMemcpyDeviceToHost, p->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(floor_out, out + ev_bytes, n4, hipMemcpyDeviceToHost, p->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(found_out, out + ev_bytes + n4, n4, hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  return e == hipSuccess ? ZFFT_OK : hip_fail(e, "detect D2H");
+  return sync_read(p, e, "detect D2H");
 }
 
 int zfft_detect_floors_device(zfft_plan *p, const float *d_rows, int32_t count, float *d_floors, void *hip_stream) {
@@ -258,7 +243,7 @@ int zfft_detect_floors_device(zfft_plan *p, const float *d_rows, int32_t count, 
   if (rc) return rc;
   rc = need_local(p);
   if (rc) return rc;
-  if (!d_rows || !d_floors || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / output / count");
+  if (!d_rows || !d_floors || count < 1 || count > kMaxDetectRows) return fail(ZFFT_EINVAL, "bad rows / output / count");
   hipStream_t st = pick_stream(p, hip_stream);
   rc = use_stream(p, st);
   if (rc) return rc;
@@ -278,25 +263,17 @@ int zfft_detect_floors(zfft_plan *p, const float *rows, int32_t count, float *fl
   if (rc) return rc;
   rc = need_local(p);
   if (rc) return rc;
-  if (!rows || !floors_out || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / output / count");
+  if (!rows || !floors_out || count < 1 || count > kMaxDetectRows) return fail(ZFFT_EINVAL, "bad rows / output / count");
   const int n_win = p->cfg.n_win, n = det_length(p);
   const size_t bytes = (size_t)count * n_win * sizeof(float);
-  if (p->dt_stage.cap < bytes || p->dt_out.cap < bytes) {
-    rc = quiesce(p);  // growing frees what an earlier call may still use
-    if (rc) return rc;
-    if (p->dt_stage.ensure(bytes) != hipSuccess || p->dt_out.ensure(bytes) != hipSuccess)
-      return fail(ZFFT_ENOMEM, "detect staging allocation failed");
-  }
-  rc = use_stream(p, p->stream);
+  const float *d_rows;
+  rc = grow(p, p->dt_out, bytes, "detect staging");
+  if (!rc) rc = stage_rows(p, rows, count, "detect staging", &d_rows);
+  if (!rc) rc = zfft_detect_floors_device(p, d_rows, count, p->dt_out.as<float>(), p->stream);
   if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(p->dt_stage.p, rows, bytes, hipMemcpyHostToDevice, p->stream);
-  if (e != hipSuccess) return hip_fail(e, "H2D rows");
-  rc = zfft_detect_floors_device(p, p->dt_stage.as<float>(), count, p->dt_out.as<float>(), p->stream);
+  rc = sync_read(p, hipMemcpyAsync(floors_out, p->dt_out.p, bytes, hipMemcpyDeviceToHost, p->stream),
+                 "detect floors D2H");
   if (rc) return rc;
-  e = hipMemcpyAsync(floors_out, p->dt_out.p, bytes, hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  if (e != hipSuccess) return hip_fail(e, "detect floors D2H");
   for (int64_t r = 0; r < count; ++r)  // the device leaves the columns beyond the row untouched
     std::fill(floors_out + r * n_win + n, floors_out + (r + 1) * n_win, std::numeric_limits<float>::quiet_NaN());
   return ZFFT_OK;
@@ -312,9 +289,8 @@ int zfft_detect_occupancy(zfft_plan *p, uint32_t *occ_out, uint64_t *rows_seen) 
   if (rc) return rc;
   hipError_t e = hipMemcpyAsync(occ_out, p->dt_occ.p, (size_t)p->cfg.n_win * sizeof(unsigned),
                                 hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  if (e != hipSuccess) return hip_fail(e, "detect occupancy read");
+  rc = sync_read(p, e, "detect occupancy read");
+  if (rc) return rc;
   if (rows_seen) *rows_seen = p->dt_rows;
   return ZFFT_OK;
 }

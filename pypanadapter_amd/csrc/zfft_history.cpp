@@ -17,7 +17,6 @@ using namespace zfft;
 
 namespace {
 
-constexpr int32_t kMaxCount = 1 << 30;               // rows per call (int row indices)
 constexpr size_t kReplayChunk = (size_t)64 << 20;    // float rows per replay step, bytes
 const float kNaN = std::numeric_limits<float>::quiet_NaN();
 
@@ -26,7 +25,7 @@ int need_on(const zfft_plan *p) {
 }
 
 void release_history(zfft_plan *p) {
-  for (zfft_plan::DevBuf *b : {&p->hs_store, &p->hs_stage, &p->hs_img, &p->hs_rgba, &p->hs_scratch, &p->hs_replay})
+  for (zfft_plan::DevBuf *b : {&p->hs_store, &p->row_stage, &p->hs_img, &p->hs_rgba, &p->hs_scratch, &p->hs_replay})
     b->release();
   p->hs_cap = p->hs_stride = 0;
   p->hs_seen = 0;
@@ -39,18 +38,6 @@ HistStore store_of(const zfft_plan *p) {
 
 uint64_t oldest_of(const zfft_plan *p) { return p->hs_seen - std::min<uint64_t>(p->hs_seen, (uint64_t)p->hs_cap); }
 
-// a grow-only buffer an enqueued call may still use: wait before it is replaced
-int grow(zfft_plan *p, zfft_plan::DevBuf &b, size_t bytes, const char *what) {
-  if (b.cap >= bytes) return ZFFT_OK;
-  int rc = quiesce(p);
-  if (rc) return rc;
-  if (b.ensure(bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ZFFT_ENOMEM, std::string(what) + " allocation failed");
-  }
-  return ZFFT_OK;
-}
-
 int window_ok(const zfft_plan *p, const zfft_history_window *w) {
   const int n = row_length(p);
   if (!w || w->col0 < 0 || w->col1 <= w->col0 || w->col1 > n || w->width < 1 || w->width > w->col1 - w->col0 ||
@@ -62,13 +49,6 @@ int window_ok(const zfft_plan *p, const zfft_history_window *w) {
   // (first + lines * rows_per_line stays far inside int64)
   if (w->first < -((int64_t)1 << 62) || w->first > ((int64_t)1 << 62)) return fail(ZFFT_EINVAL, "history window: first");
   return ZFFT_OK;
-}
-
-// the device copy and the wait every synchronous read ends with
-int finish_copy(zfft_plan *p, hipError_t e, const char *what) {
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  return e == hipSuccess ? ZFFT_OK : hip_fail(e, what);
 }
 
 }  // namespace
@@ -121,7 +101,7 @@ int zfft_history_push_device(zfft_plan *p, const float *d_rows, int32_t count, v
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!d_rows || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / count");
+  if (!d_rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
   // a push longer than the ring keeps its last hs_cap rows
   const int64_t skip = std::max<int64_t>(0, (int64_t)count - p->hs_cap);
   hipStream_t st = pick_stream(p, hip_stream);
@@ -142,17 +122,12 @@ int zfft_history_push(zfft_plan *p, const float *rows, int32_t count) {
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!rows || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / count");
-  const size_t bytes = (size_t)count * p->cfg.n_win * sizeof(float);
-  rc = grow(p, p->hs_stage, bytes, "history row staging");
+  if (!rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
+  const float *d_rows;
+  rc = stage_rows(p, rows, count, "history row staging", &d_rows);
+  if (!rc) rc = zfft_history_push_device(p, d_rows, count, p->stream);
   if (rc) return rc;
-  rc = use_stream(p, p->stream);  // the staging may still be read by the previous call
-  if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(p->hs_stage.p, rows, bytes, hipMemcpyHostToDevice, p->stream);
-  if (e != hipSuccess) return hip_fail(e, "H2D rows");
-  rc = zfft_history_push_device(p, p->hs_stage.as<float>(), count, p->stream);
-  if (rc) return rc;
-  e = hipStreamSynchronize(p->stream);
+  hipError_t e = hipStreamSynchronize(p->stream);
   return e == hipSuccess ? ZFFT_OK : hip_fail(e, "sync");
 }
 
@@ -170,7 +145,7 @@ int zfft_history_read_device(zfft_plan *p, int64_t first, int32_t count, float *
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!d_rows || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / count");
+  if (!d_rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
   if (first < 0 || (uint64_t)first < oldest_of(p) || (uint64_t)first + (uint64_t)count > p->hs_seen)
     return fail(ZFFT_EINVAL, "history read: rows outside [oldest, rows_seen)");
   hipStream_t st = pick_stream(p, hip_stream);
@@ -189,22 +164,22 @@ int zfft_history_read(zfft_plan *p, int64_t first, int32_t count, float *rows_ou
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!rows_out || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / count");
+  if (!rows_out || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
   const size_t cells = (size_t)count * p->cfg.n_win;
-  rc = grow(p, p->hs_stage, cells * sizeof(float), "history row staging");
+  rc = grow(p, p->row_stage, cells * sizeof(float), "history row staging");
   if (rc) return rc;
   rc = use_stream(p, p->stream);
   if (rc) return rc;
   if (row_length(p) < p->cfg.n_win) {  // the columns at or beyond the row length read as NaN
-    hipError_t e = launch_view_fill(p->hs_stage.as<float>(), (int64_t)cells, kNaN, p->stream);
+    hipError_t e = launch_view_fill(p->row_stage.as<float>(), (int64_t)cells, kNaN, p->stream);
     if (e != hipSuccess) return hip_fail(e, "history fill");
     rc = done_on(p, p->stream);
     if (rc) return rc;
   }
-  rc = zfft_history_read_device(p, first, count, p->hs_stage.as<float>(), p->stream);
+  rc = zfft_history_read_device(p, first, count, p->row_stage.as<float>(), p->stream);
   if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(rows_out, p->hs_stage.p, cells * sizeof(float), hipMemcpyDeviceToHost, p->stream);
-  return finish_copy(p, e, "history read");
+  hipError_t e = hipMemcpyAsync(rows_out, p->row_stage.p, cells * sizeof(float), hipMemcpyDeviceToHost, p->stream);
+  return sync_read(p, e, "history read");
 }
 
 int zfft_history_view_device(zfft_plan *p, const zfft_history_window *w, float *d_img, void *hip_stream) {
@@ -261,7 +236,7 @@ int zfft_history_view(zfft_plan *p, const zfft_history_window *w, float *img_out
   rc = zfft_history_view_device(p, w, p->hs_img.as<float>(), p->stream);
   if (rc) return rc;
   hipError_t e = hipMemcpyAsync(img_out, p->hs_img.p, bytes, hipMemcpyDeviceToHost, p->stream);
-  return finish_copy(p, e, "history view");
+  return sync_read(p, e, "history view");
 }
 
 int zfft_history_render(zfft_plan *p, const zfft_history_window *w, uint8_t *rgba_out) {
@@ -285,7 +260,7 @@ int zfft_history_render(zfft_plan *p, const zfft_history_window *w, uint8_t *rgb
   hipError_t e = launch_waterfall_render(p->hs_img.as<float>(), w->lines, w->width, 0, p->lut_d.p, lo, scale,
                                          p->hs_rgba.p, p->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(rgba_out, p->hs_rgba.p, px * 4, hipMemcpyDeviceToHost, p->stream);
-  return finish_copy(p, e, "history render");
+  return sync_read(p, e, "history render");
 }
 
 int zfft_history_replay_viewport(zfft_plan *p, int64_t first) {

@@ -1,7 +1,9 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
-// zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and
-// the HIP kernels (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, detect_kernels.hip,
-// view_kernels.hip, history_kernels.hip).  Not part of the C-ABI.
+// zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp,
+// zfft_history.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
+// (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, fc2_kernels.hip,
+// detect_kernels.hip, detect_local_kernels.hip, track_kernels.hip, view_kernels.hip,
+// history_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

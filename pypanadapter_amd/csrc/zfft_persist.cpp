@@ -13,7 +13,6 @@ using namespace zfft;
 namespace {
 
 constexpr int kMaxLevels = 256;         // 64 KB of LDS counters per workgroup
-constexpr int32_t kMaxCount = 1 << 30;  // rows per push (int row indices)
 
 int need_on(const zfft_plan *p) {
   return p->ps_levels ? ZFFT_OK : fail(ZFFT_EINVAL, "persistence is off (zfft_plan_persistence)");
@@ -44,7 +43,7 @@ int zfft_plan_persistence(zfft_plan *p, int32_t levels, double db_min, double db
     rc = quiesce(p);  // an enqueued push may still add to the table
     if (rc) return rc;
     p->ps_hist.release();
-    p->ps_stage.release();
+    p->row_stage.release();
     p->ps_levels = 0;
     p->ps_rows = 0;
     return ZFFT_OK;
@@ -55,14 +54,9 @@ int zfft_plan_persistence(zfft_plan *p, int32_t levels, double db_min, double db
   const float inv = (float)((double)levels / (db_max - db_min));
   if (!std::isfinite(inv) || !std::isfinite((float)db_min))
     return fail(ZFFT_EINVAL, "persistence: the level width does not fit float32");
-  if ((size_t)levels * p->cfg.n_win * sizeof(unsigned) > p->ps_hist.cap) {
-    rc = quiesce(p);  // growing frees the old table
-    if (rc) return rc;
-  }
-  if (p->ps_hist.ensure((size_t)levels * p->cfg.n_win * sizeof(unsigned)) != hipSuccess) {
-    p->ps_levels = 0;
-    return fail(ZFFT_ENOMEM, "persistence table allocation failed");
-  }
+  rc = grow(p, p->ps_hist, (size_t)levels * p->cfg.n_win * sizeof(unsigned), "persistence table");
+  if (rc == ZFFT_ENOMEM) p->ps_levels = 0;
+  if (rc) return rc;
   p->ps_levels = levels;
   p->ps_lo = (float)db_min;
   p->ps_inv = inv;
@@ -81,7 +75,7 @@ int zfft_persistence_push_device(zfft_plan *p, const float *d_rows, int32_t coun
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!d_rows || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / count");
+  if (!d_rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
   hipStream_t st = pick_stream(p, hip_stream);
   rc = use_stream(p, st);  // after the table's zeroing and earlier pushes, on any stream
   if (rc) return rc;
@@ -103,21 +97,12 @@ int zfft_persistence_push(zfft_plan *p, const float *rows, int32_t count) {
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!rows || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / count");
-  const size_t bytes = (size_t)count * p->cfg.n_win * sizeof(float);
-  if (p->ps_stage.cap < bytes) {
-    rc = quiesce(p);  // growing frees the staging an earlier push may still read
-    if (rc) return rc;
-    if (p->ps_stage.ensure(bytes) != hipSuccess)
-      return fail(ZFFT_ENOMEM, "persistence row staging allocation failed");
-  }
-  rc = use_stream(p, p->stream);  // the staging may still be read by the previous push
+  if (!rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
+  const float *d_rows;
+  rc = stage_rows(p, rows, count, "persistence row staging", &d_rows);
+  if (!rc) rc = zfft_persistence_push_device(p, d_rows, count, p->stream);
   if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(p->ps_stage.p, rows, bytes, hipMemcpyHostToDevice, p->stream);
-  if (e != hipSuccess) return hip_fail(e, "H2D rows");
-  rc = zfft_persistence_push_device(p, p->ps_stage.as<float>(), count, p->stream);
-  if (rc) return rc;
-  e = hipStreamSynchronize(p->stream);
+  hipError_t e = hipStreamSynchronize(p->stream);
   return e == hipSuccess ? ZFFT_OK : hip_fail(e, "sync");
 }
 
@@ -153,9 +138,8 @@ int zfft_persistence_read(zfft_plan *p, uint32_t *hist_out, uint64_t *rows_seen)
   if (rc) return rc;
   hipError_t e = hipMemcpyAsync(hist_out, p->ps_hist.p, table_cells(p) * sizeof(unsigned),
                                 hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  if (e != hipSuccess) return hip_fail(e, "persistence read");
+  rc = sync_read(p, e, "persistence read");
+  if (rc) return rc;
   if (rows_seen) *rows_seen = p->ps_rows;
   return ZFFT_OK;
 }

@@ -1,5 +1,6 @@
 // zfft_plan.cpp -- the plan of libzfft.so: create / destroy, its settings, the stream ordering
-// helpers and the host entry points (zfft_process, zfft_decimate).  The plan object is in
+// helpers, the buffer and staging helpers of the row consumers (grow, sync_read, stage_rows,
+// pin_rows) and the host entry points (zfft_process, zfft_decimate).  The plan object is in
 // zfft_plan.h, the decimator in zfft_decim.cpp (schedule choice: zfft_schedule.cpp), the Welch
 // launches in zfft_welch.cpp (form choice: zfft_welch_plan.cpp), the waterfall in
 // zfft_waterfall.cpp.
@@ -8,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -79,6 +81,54 @@ int quiesce(zfft_plan *p) {
   ++p->n_quiesce;
   hipError_t e = hipEventSynchronize(p->done_ev);
   return e == hipSuccess ? ZFFT_OK : hip_fail(e, "hipEventSynchronize");
+}
+
+int grow(zfft_plan *p, DevBuf &b, size_t bytes, const char *what) {
+  if (b.cap >= bytes) return ZFFT_OK;
+  int rc = quiesce(p);  // growing frees what an enqueued call may still use
+  if (rc) return rc;
+  if (b.ensure(bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ZFFT_ENOMEM, std::string(what) + " allocation failed");
+  }
+  return ZFFT_OK;
+}
+
+int sync_read(zfft_plan *p, hipError_t e, const char *what) {
+  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+  return e == hipSuccess ? ZFFT_OK : hip_fail(e, what);
+}
+
+int stage_rows(zfft_plan *p, const float *rows, int32_t count, const char *what, const float **d_rows) {
+  const size_t bytes = (size_t)count * p->cfg.n_win * sizeof(float);
+  int rc = grow(p, p->row_stage, bytes, what);
+  if (rc) return rc;
+  rc = use_stream(p, p->stream);  // the staging may still be read by the previous call
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(p->row_stage.p, rows, bytes, hipMemcpyHostToDevice, p->stream);
+  if (e != hipSuccess) return hip_fail(e, "H2D rows");
+  *d_rows = p->row_stage.as<float>();
+  return ZFFT_OK;
+}
+
+int pin_rows(zfft_plan *p, const float *rows, size_t bytes, const float **d_rows) {
+  if (bytes > p->row_pin_cap) {
+    int rc = quiesce(p);
+    if (rc) return rc;
+    if (p->row_pin) (void)hipHostFree(p->row_pin);
+    p->row_pin = nullptr;
+    p->row_pin_cap = 0;
+    if (hipHostMalloc((void **)&p->row_pin, bytes, hipHostMallocDefault) != hipSuccess)
+      return fail(ZFFT_ENOMEM, "page-locked row staging allocation failed");
+    p->row_pin_cap = bytes;
+  }
+  std::memcpy(p->row_pin, rows, bytes);
+  void *d = nullptr;
+  hipError_t e = hipHostGetDevicePointer(&d, p->row_pin, 0);
+  if (e != hipSuccess) return hip_fail(e, "hipHostGetDevicePointer");
+  *d_rows = (const float *)d;
+  return ZFFT_OK;
 }
 
 int enter(zfft_plan *p) {

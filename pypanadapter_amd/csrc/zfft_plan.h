@@ -106,7 +106,8 @@ struct zfft_plan {
   DevBuf lut_d, rgba, al_hist, al_bins;
   DevBuf img64;                    // float64 image of the display entries
   float *row_pin = nullptr;        // page-locked staging of host rows the display kernels read
-  size_t row_pin_cap = 0;          //   in place (no H2D copy command); bytes
+  size_t row_pin_cap = 0;          //   in place (no H2D copy command); bytes (pin_rows)
+  DevBuf row_stage;                // device staging of host rows, shared by the row consumers (stage_rows)
   // persistence spectrum (zfft_plan_persistence; zfft_persist.cpp): ps_levels x n_win uint32
   // counts, level-major; 0 levels = off (no buffer).  ps_lo / ps_inv are the binning rule's
   // float32 constants; ps_rows the rows pushed (host side: pushes and decays are in call order)
@@ -114,15 +115,15 @@ struct zfft_plan {
   float ps_lo = 0.f, ps_inv = 0.f;
   uint64_t ps_rows = 0;
   int ps_slices = 0;               // row slices of the last push (test hook zfft__plan_persist_slices)
-  DevBuf ps_hist, ps_stage;        // the table; device staging of zfft_persistence_push's host rows
+  DevBuf ps_hist;                  // the table
   // row detector (zfft_plan_detect; zfft_detect.cpp): dt_k = max_per_row, 0 = off (no buffer).
-  // dt_occ holds n_win uint32 counts, dt_rows the rows seen (host side, in call order); dt_stage
-  // and dt_out are the device staging of zfft_detect's host rows and outputs
+  // dt_occ holds n_win uint32 counts, dt_rows the rows seen (host side, in call order); dt_out
+  // is the device staging of zfft_detect's outputs
   int dt_k = 0, dt_min_width = 1;
   double dt_q = 0.5;
   float dt_thr = 0.f;
   uint64_t dt_rows = 0;
-  DevBuf dt_occ, dt_stage, dt_out;
+  DevBuf dt_occ, dt_out;
   // the local floor (zfft_plan_detect_local): dt_h = half_window, 0 = the row-global floor (no
   // buffer).  dt_floors holds the floors of a pass, at most dt_local_cap bytes (0 = the default,
   // kDetectLocalScratch; test hook zfft__plan_detect_local_cap)
@@ -149,17 +150,17 @@ struct zfft_plan {
   uint64_t vw_rows = 0, vw_lines = 0;
   int vw_pending = 0;
   int vw_kind = 0;                 // ViewForm::kind of the last push (test hook zfft__plan_view_form)
-  DevBuf vw_ring, vw_img, vw_tr, vw_pend, vw_scratch, vw_stage, vw_rgba;
+  DevBuf vw_ring, vw_img, vw_tr, vw_pend, vw_scratch, vw_rgba;
   // row history (zfft_plan_history; zfft_history.cpp): hs_cap = 0 is off (no buffer).  hs_store
   // holds hs_cap slots of hs_stride elements in hs_q.format, row R in slot R mod hs_cap; hs_seen
-  // counts the rows pushed (host side: pushes are in call order).  hs_stage is the device staging
-  // of host rows (push, read), hs_img / hs_rgba a host view's image and pixels, hs_scratch a sliced
-  // view's partials, hs_replay the float rows of zfft_history_replay_viewport
+  // counts the rows pushed (host side: pushes are in call order).  hs_img / hs_rgba are a host
+  // view's image and pixels, hs_scratch a sliced view's partials, hs_replay the float rows of
+  // zfft_history_replay_viewport; zfft_history_read stages its rows in row_stage
   int64_t hs_cap = 0, hs_stride = 0;
   zfft::HistQuant hs_q;
   uint64_t hs_seen = 0;
   int hs_kind = 0;                 // HistForm::kind of the last view (test hook zfft__plan_history_form)
-  DevBuf hs_store, hs_stage, hs_img, hs_rgba, hs_scratch, hs_replay;
+  DevBuf hs_store, hs_img, hs_rgba, hs_scratch, hs_replay;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the
@@ -196,6 +197,24 @@ int done_on(zfft_plan *p, hipStream_t st);
 // overwrites a table that work may still read).
 int quiesce(zfft_plan *p);
 int enter(zfft_plan *p);  // null check + hipSetDevice
+// Grows a buffer an enqueued call may still use: nothing when it holds `bytes`, else quiesce, then
+// a new allocation; ZFFT_ENOMEM "<what> allocation failed" (HIP's sticky error cleared).
+int grow(zfft_plan *p, DevBuf &b, size_t bytes, const char *what);
+// Ends a synchronous read: given the status of the copies enqueued on the plan's stream, marks the
+// plan's work done there and waits for it; a failure is ZFFT_EHIP "<what>: ...".
+int sync_read(zfft_plan *p, hipError_t e, const char *what);
+// `count` host rows of n_win floats into the plan's one device staging row_stage (grown under
+// `what`), copied on the plan's stream after the plan's earlier work; *d_rows = the staging.
+// Every row consumer shares the buffer, and zfft_history_read uses it for the other direction.
+// That is safe only while every user copies and launches on p->stream and waits for that stream
+// before it returns: a new user must do the same, or take a buffer of its own.
+int stage_rows(zfft_plan *p, const float *rows, int32_t count, const char *what, const float **d_rows);
+// `bytes` of host rows into the page-locked row_pin, which the display kernels read in place;
+// *d_rows = its device address.  A growth waits for the plan's work before it frees.  The callers
+// wait for their kernels before they return: no kernel still reads row_pin at the next call.
+int pin_rows(zfft_plan *p, const float *rows, size_t bytes, const float **d_rows);
+// Rows per call: int row indices; the detector's count * max_per_row records stay below 2^31.
+constexpr int32_t kMaxPushRows = 1 << 30, kMaxDetectRows = 1 << 26;
 // Real input at zoom 1 takes scipy.signal.welch's one-sided branch.
 inline bool onesided(const zfft_plan *p) { return p->cfg.in_dtype == kInF32R && p->K == 0; }
 int row_length(const zfft_plan *p);  // valid entries per row

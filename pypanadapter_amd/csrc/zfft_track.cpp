@@ -16,8 +16,6 @@ using namespace zfft;
 
 namespace {
 
-constexpr int32_t kMaxCount = 1 << 26;  // rows per call, as the detector's
-
 // the carried state in tk_state
 constexpr size_t kOffCtr = 0, kOffFound = 64, kOffParent = 128, kOffEv = kOffParent + 4 * kTrackFrontier,
                  kOffOpen = kOffEv + 16 * kTrackFrontier, kStateBytes = kOffOpen + sizeof(TrackOpen) * kTrackFrontier;
@@ -59,9 +57,7 @@ int read_counters(zfft_plan *p, TrackCounters *c) {
   int rc = use_stream(p, p->stream);
   if (rc) return rc;
   hipError_t e = hipMemcpyAsync(c, p->tk_state.as<char>() + kOffCtr, sizeof(*c), hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  return e == hipSuccess ? ZFFT_OK : hip_fail(e, "track counters read");
+  return sync_read(p, e, "track counters read");
 }
 
 }  // namespace
@@ -130,17 +126,13 @@ int zfft_track_push_device(zfft_plan *p, const int32_t *d_found, const zfft_emis
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!d_found || !d_events || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad found / records / count");
+  if (!d_found || !d_events || count < 1 || count > kMaxDetectRows) return fail(ZFFT_EINVAL, "bad found / records / count");
   const int K = p->dt_k, gap = p->tk_gap;
   const TrackForm f = choose_track(K, gap, count);
   if (!f.ok()) return fail(ZFFT_EINVAL, "track: no form for this call");
   const int rows0 = std::min(count, f.pass_rows);
-  const size_t need = track_scratch_bytes(K, gap, rows0);
-  if (p->tk_scratch.cap < need) {
-    rc = quiesce(p);  // growing frees what an earlier push may still use
-    if (rc) return rc;
-    if (p->tk_scratch.ensure(need) != hipSuccess) return fail(ZFFT_ENOMEM, "track scratch allocation failed");
-  }
+  rc = grow(p, p->tk_scratch, track_scratch_bytes(K, gap, rows0), "track scratch");
+  if (rc) return rc;
   hipStream_t st = pick_stream(p, hip_stream);
   rc = use_stream(p, st);
   if (rc) return rc;
@@ -182,7 +174,7 @@ int zfft_track_push(zfft_plan *p, const int32_t *found, const zfft_emission *eve
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!found || !events || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad found / records / count");
+  if (!found || !events || count < 1 || count > kMaxDetectRows) return fail(ZFFT_EINVAL, "bad found / records / count");
   const int K = p->dt_k;
   for (int64_t r = 0; r < count; ++r) {  // rule 9 on the slots the tracker will use
     const int used = std::min(std::max(found[r], 0), K);
@@ -195,12 +187,8 @@ int zfft_track_push(zfft_plan *p, const int32_t *found, const zfft_emission *eve
     }
   }
   const size_t ev_bytes = (size_t)count * K * sizeof(zfft_emission), n4 = (size_t)count * 4;
-  if (p->tk_stage.cap < ev_bytes + n4) {
-    rc = quiesce(p);  // growing frees what an earlier call may still use
-    if (rc) return rc;
-    if (p->tk_stage.ensure(ev_bytes + n4) != hipSuccess) return fail(ZFFT_ENOMEM, "track staging allocation failed");
-  }
-  rc = use_stream(p, p->stream);  // the staging may still be read by the previous call
+  rc = grow(p, p->tk_stage, ev_bytes + n4, "track staging");
+  if (!rc) rc = use_stream(p, p->stream);  // the staging may still be read by the previous call
   if (rc) return rc;
   char *d = p->tk_stage.as<char>();
   hipError_t e = hipMemcpyAsync(d, events, ev_bytes, hipMemcpyHostToDevice, p->stream);

@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <limits>
 
 #include "zfft.h"
@@ -16,7 +15,6 @@ using namespace zfft;
 
 namespace {
 
-constexpr int32_t kMaxCount = 1 << 30;  // rows per push (int row indices)
 const float kNaN = std::numeric_limits<float>::quiet_NaN();
 
 int need_on(const zfft_plan *p) {
@@ -45,19 +43,12 @@ int reset_view(zfft_plan *p) {
 }
 
 void release_view(zfft_plan *p) {
-  for (zfft_plan::DevBuf *b : {&p->vw_ring, &p->vw_img, &p->vw_tr, &p->vw_pend, &p->vw_scratch, &p->vw_stage,
-                               &p->vw_rgba})
+  for (zfft_plan::DevBuf *b : {&p->vw_ring, &p->vw_img, &p->vw_tr, &p->vw_pend, &p->vw_scratch, &p->vw_rgba,
+                               &p->row_stage})
     b->release();
   p->vw_h = p->vw_w = 0;
   p->vw_rows = p->vw_lines = 0;
   p->vw_pending = 0;
-}
-
-// the device copy and the wait every synchronous read ends with
-int finish_copy(zfft_plan *p, hipError_t e, const char *what) {
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  return e == hipSuccess ? ZFFT_OK : hip_fail(e, what);
 }
 
 }  // namespace
@@ -111,7 +102,7 @@ int zfft_viewport_push_device(zfft_plan *p, const float *d_rows, int32_t count, 
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!d_rows || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / count");
+  if (!d_rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
   ViewGeom g{};
   g.n_win = p->cfg.n_win;
   g.col0 = p->vw_c0;
@@ -129,12 +120,8 @@ int zfft_viewport_push_device(zfft_plan *p, const float *d_rows, int32_t count, 
   const ViewForm f = choose_view(count, g.m, g.pending, g.span, g.width);
   if (!f.ok()) return fail(ZFFT_EINTERNAL, "viewport: no form for this push");
   g.direct = view_direct(g, f) ? 1 : 0;
-  const size_t sb = view_scratch_bytes(f, g.width);
-  if (p->vw_scratch.cap < sb) {
-    rc = quiesce(p);  // growing frees the scratch an earlier push may still use
-    if (rc) return rc;
-    if (p->vw_scratch.ensure(sb) != hipSuccess) return fail(ZFFT_ENOMEM, "viewport scratch allocation failed");
-  }
+  rc = grow(p, p->vw_scratch, view_scratch_bytes(f, g.width), "viewport scratch");
+  if (rc) return rc;
   hipStream_t st = pick_stream(p, hip_stream);
   rc = use_stream(p, st);  // after the fills and earlier pushes, on any stream
   if (rc) return rc;
@@ -163,20 +150,12 @@ int zfft_viewport_push(zfft_plan *p, const float *rows, int32_t count) {
   if (rc) return rc;
   rc = need_on(p);
   if (rc) return rc;
-  if (!rows || count < 1 || count > kMaxCount) return fail(ZFFT_EINVAL, "bad rows / count");
-  const size_t bytes = (size_t)count * p->cfg.n_win * sizeof(float);
-  if (p->vw_stage.cap < bytes) {
-    rc = quiesce(p);  // growing frees the staging an earlier push may still read
-    if (rc) return rc;
-    if (p->vw_stage.ensure(bytes) != hipSuccess) return fail(ZFFT_ENOMEM, "viewport row staging allocation failed");
-  }
-  rc = use_stream(p, p->stream);  // the staging may still be read by the previous push
+  if (!rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
+  const float *d_rows;
+  rc = stage_rows(p, rows, count, "viewport row staging", &d_rows);
+  if (!rc) rc = zfft_viewport_push_device(p, d_rows, count, p->stream);
   if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(p->vw_stage.p, rows, bytes, hipMemcpyHostToDevice, p->stream);
-  if (e != hipSuccess) return hip_fail(e, "H2D rows");
-  rc = zfft_viewport_push_device(p, p->vw_stage.as<float>(), count, p->stream);
-  if (rc) return rc;
-  e = hipStreamSynchronize(p->stream);
+  hipError_t e = hipStreamSynchronize(p->stream);
   return e == hipSuccess ? ZFFT_OK : hip_fail(e, "sync");
 }
 
@@ -202,7 +181,7 @@ int zfft_viewport_read(zfft_plan *p, float *img_out) {
                                        p->stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(img_out, p->vw_img.p, cells(p) * sizeof(float), hipMemcpyDeviceToHost, p->stream);
-  return finish_copy(p, e, "viewport read");
+  return sync_read(p, e, "viewport read");
 }
 
 int zfft_viewport_traces(zfft_plan *p, float *last, float *max_hold, float *min_hold) {
@@ -218,7 +197,7 @@ int zfft_viewport_traces(zfft_plan *p, float *last, float *max_hold, float *min_
     if (out[k])
       e = hipMemcpyAsync(out[k], p->vw_tr.as<float>() + (size_t)k * p->vw_w, (size_t)p->vw_w * sizeof(float),
                          hipMemcpyDeviceToHost, p->stream);
-  return finish_copy(p, e, "viewport traces");
+  return sync_read(p, e, "viewport traces");
 }
 
 int zfft_viewport_hold_reset(zfft_plan *p) {
@@ -264,32 +243,14 @@ int zfft_viewport_push_render(zfft_plan *p, const float *rows, int32_t count, ui
   rc = need_on(p);
   if (rc) return rc;
   if (!rgba_out) return fail(ZFFT_EINVAL, "null output");
-  if (count < 0 || count > kMaxCount || (count > 0 && !rows)) return fail(ZFFT_EINVAL, "bad rows / count");
+  if (count < 0 || count > kMaxPushRows || (count > 0 && !rows)) return fail(ZFFT_EINVAL, "bad rows / count");
   const size_t bytes = cells(p) * 4;
-  if (p->vw_rgba.cap < bytes) {
-    rc = quiesce(p);  // (an enqueued render of the caller's never uses vw_rgba; the order is kept all the same)
-    if (rc) return rc;
-    if (p->vw_rgba.ensure(bytes) != hipSuccess) return fail(ZFFT_ENOMEM, "render buffer allocation failed");
-  }
-  hipError_t e;
+  rc = grow(p, p->vw_rgba, bytes, "render buffer");  // (an enqueued render of the caller's never uses vw_rgba)
+  if (rc) return rc;
   if (count > 0) {
-    const size_t rb = (size_t)count * p->cfg.n_win * sizeof(float);
-    if (rb > p->row_pin_cap) {
-      rc = quiesce(p);
-      if (rc) return rc;
-      if (p->row_pin) (void)hipHostFree(p->row_pin);
-      p->row_pin = nullptr;
-      p->row_pin_cap = 0;
-      e = hipHostMalloc((void **)&p->row_pin, rb, hipHostMallocDefault);
-      if (e != hipSuccess) return fail(ZFFT_ENOMEM, "page-locked row staging allocation failed");
-      p->row_pin_cap = rb;
-    }
-    // every display call waits for its kernels before returning: no kernel still reads row_pin
-    std::memcpy(p->row_pin, rows, rb);
-    void *d = nullptr;
-    e = hipHostGetDevicePointer(&d, p->row_pin, 0);
-    if (e != hipSuccess) return hip_fail(e, "hipHostGetDevicePointer");
-    rc = zfft_viewport_push_device(p, (const float *)d, count, p->stream);
+    const float *d_rows;
+    rc = pin_rows(p, rows, (size_t)count * p->cfg.n_win * sizeof(float), &d_rows);
+    if (!rc) rc = zfft_viewport_push_device(p, d_rows, count, p->stream);
     if (rc) return rc;
   }
   // a small image into page-locked host memory is written by the kernel in place; a larger one
@@ -301,8 +262,8 @@ int zfft_viewport_push_render(zfft_plan *p, const float *rows, int32_t count, ui
     (void)hipGetLastError(), hout = nullptr;
   rc = zfft_viewport_render_device(p, (uint8_t *)dout, p->stream);
   if (rc) return rc;
-  e = hout ? hipSuccess : hipMemcpyAsync(rgba_out, dout, bytes, hipMemcpyDeviceToHost, p->stream);
-  return finish_copy(p, e, "viewport image copy");
+  hipError_t e = hout ? hipSuccess : hipMemcpyAsync(rgba_out, dout, bytes, hipMemcpyDeviceToHost, p->stream);
+  return sync_read(p, e, "viewport image copy");
 }
 
 int zfft_viewport_render(zfft_plan *p, uint8_t *rgba_out) { return zfft_viewport_push_render(p, nullptr, 0, rgba_out); }

@@ -159,9 +159,7 @@ int zfft_waterfall_read(zfft_plan *p, float *img_out) {
   if (e == hipSuccess)
     e = hipMemcpyAsync(img_out, p->img.p, (size_t)p->H * p->W * sizeof(float),
                        hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  return e == hipSuccess ? ZFFT_OK : hip_fail(e, "waterfall read");
+  return sync_read(p, e, "waterfall read");
 }
 
 int zfft_colormap_lut(const char *name, uint8_t *lut_rgba) {
@@ -236,21 +234,8 @@ int push_emit(zfft_plan *p, const float *rows, int32_t count, bool f64, void *ho
   if (e != hipSuccess) return fail(ZFFT_ENOMEM, "image buffer allocation failed");
   const float *drows = nullptr;
   if (count > 0) {
-    const size_t rb = (size_t)count * W * sizeof(float);
-    if (rb > p->row_pin_cap) {
-      if (p->row_pin) (void)hipHostFree(p->row_pin);
-      p->row_pin = nullptr;
-      p->row_pin_cap = 0;
-      e = hipHostMalloc((void **)&p->row_pin, rb, hipHostMallocDefault);
-      if (e != hipSuccess) return fail(ZFFT_ENOMEM, "page-locked row staging allocation failed");
-      p->row_pin_cap = rb;
-    }
-    // every display call waits for its kernels before returning: no kernel still reads row_pin
-    std::memcpy(p->row_pin, rows, rb);
-    void *d = nullptr;
-    e = hipHostGetDevicePointer(&d, p->row_pin, 0);
-    if (e != hipSuccess) return hip_fail(e, "hipHostGetDevicePointer");
-    drows = (const float *)d;
+    rc = pin_rows(p, rows, (size_t)count * W * sizeof(float), &drows);
+    if (rc) return rc;
   }
   rc = use_stream(p, p->stream);
   if (rc) return rc;
@@ -279,9 +264,7 @@ int push_emit(zfft_plan *p, const float *rows, int32_t count, bool f64, void *ho
   if (e != hipSuccess) return hip_fail(e, "waterfall push + emit");
   if (drows) p->off = ((p->off + p->cfg.scroll) % H + H) % H;
   if (!hout) e = hipMemcpyAsync(host_out, dout, bytes, hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  return e == hipSuccess ? ZFFT_OK : hip_fail(e, "waterfall image copy");
+  return sync_read(p, e, "waterfall image copy");
 }
 }  // namespace
 
@@ -325,9 +308,7 @@ int zfft_waterfall_render(zfft_plan *p, uint8_t *rgba_out) {
   rc = zfft_waterfall_render_device(p, p->rgba.as<uint8_t>(), p->stream);
   if (rc) return rc;
   e = hipMemcpyAsync(rgba_out, p->rgba.p, bytes, hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  return e == hipSuccess ? ZFFT_OK : hip_fail(e, "render copy");
+  return sync_read(p, e, "render copy");
 }
 
 int zfft_host_alloc(size_t bytes, void **out) {
@@ -403,9 +384,8 @@ int zfft_waterfall_autolevel(zfft_plan *p, double *minlev, double *maxlev) {
   if (e == hipSuccess)
     e = launch_autolevel_hist_lo(p->ring.as<float>(), n, p->al_bins.as<unsigned>(), nb, p->al_hist.as<unsigned>(), p->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(h2.data(), p->al_hist.p, (size_t)nb * 65536 * sizeof(unsigned), hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = done_on(p, p->stream) == ZFFT_OK ? hipSuccess : hipErrorUnknown;
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  if (e != hipSuccess) return hip_fail(e, "autolevel pass 2");
+  rc = sync_read(p, e, "autolevel pass 2");
+  if (rc) return rc;
   double val[4];
   for (int r = 0; r < 4; ++r) {
     const unsigned *hb = h2.data() + (size_t)slot[r] * 65536;

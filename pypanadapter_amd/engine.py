@@ -37,6 +37,20 @@ def _window_spec(window):
     return _lib.WINDOW_KINDS[name], (p[0], p[1]), None
 
 
+def full_rows(rows, n_win: int, row_length: int) -> np.ndarray:
+    """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row), as
+    C-contiguous float32 of n_win columns."""
+    r = np.asarray(rows, dtype=np.float32)
+    r = r.reshape(-1, r.shape[-1])
+    if r.shape[1] != n_win:
+        if r.shape[1] != row_length:
+            raise ValueError("rows must be n_win or row_length wide")
+        full = np.full((r.shape[0], n_win), np.nan, dtype=np.float32)  # the tail is never read
+        full[:, :r.shape[1]] = r
+        r = full
+    return np.ascontiguousarray(r)
+
+
 # in_dtype name -> (zfft_config.in_dtype, numpy element type of the host array)
 IN_DTYPES = {"complex64": (0, np.complex64), "complex32": (1, np.float16), "cu8": (2, np.uint8),
              "f32": (3, np.float32)}
@@ -413,15 +427,7 @@ class ZoomFFT:
     def persistence_push(self, rows) -> None:
         """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row),
         binned into the table; synchronous."""
-        r = np.asarray(rows, dtype=np.float32)
-        r = r.reshape(-1, r.shape[-1])
-        if r.shape[1] != self.n_win:
-            if r.shape[1] != self.row_length:
-                raise ValueError("rows must be n_win or row_length wide")
-            full = np.full((r.shape[0], self.n_win), np.nan, dtype=np.float32)  # the tail is never read
-            full[:, :r.shape[1]] = r
-            r = full
-        r = np.ascontiguousarray(r)
+        r = full_rows(rows, self.n_win, self.row_length)
         check(self.lib.zfft_persistence_push(self._plan, r.ctypes.data_as(ctypes.c_void_p), r.shape[0]),
               "zfft_persistence_push")
 
@@ -481,23 +487,11 @@ class ZoomFFT:
               "zfft_detect_local_shape")
         return h.value, g.value
 
-    def _detect_rows_arg(self, rows):
-        """Host rows as contiguous float32 (count, n_win); row_length-wide rows get a NaN tail."""
-        r = np.asarray(rows, dtype=np.float32)
-        r = r.reshape(-1, r.shape[-1])
-        if r.shape[1] != self.n_win:
-            if r.shape[1] != self.row_length:
-                raise ValueError("rows must be n_win or row_length wide")
-            full = np.full((r.shape[0], self.n_win), np.nan, dtype=np.float32)  # the tail is never read
-            full[:, :r.shape[1]] = r
-            r = full
-        return np.ascontiguousarray(r)
-
     def detect_floors(self, rows) -> np.ndarray:
         """float32 (count, n_win): the local floor of every column of host rows (as `detect`
         takes them), NaN where a column has no finite reference cell and at or beyond
         row_length; local mode only; synchronous.  No occupancy, no rows_seen."""
-        r = self._detect_rows_arg(rows)
+        r = full_rows(rows, self.n_win, self.row_length)
         out = np.empty_like(r)
         check(self.lib.zfft_detect_floors(self._plan, r.ctypes.data_as(ctypes.c_void_p), r.shape[0],
                                           out.ctypes.data_as(ctypes.c_void_p)), "zfft_detect_floors")
@@ -521,7 +515,7 @@ class ZoomFFT:
         (floor float32[count], found int32[count], events), events a structured array of shape
         (count, max_per_row) with fields first, last, peak, peak_db; synchronous."""
         K = self.detect_shape()[0]
-        r = self._detect_rows_arg(rows)
+        r = full_rows(rows, self.n_win, self.row_length)
         count = r.shape[0]
         floor = np.empty(count, dtype=np.float32)
         found = np.empty(count, dtype=np.int32)
@@ -639,23 +633,10 @@ class ZoomFFT:
         check(self.lib.zfft_viewport_shape(self._plan, ctypes.byref(h), ctypes.byref(w)), "zfft_viewport_shape")
         return h.value, w.value
 
-    def _full_rows(self, rows) -> np.ndarray:
-        """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row), as
-        C-contiguous float32 of n_win columns."""
-        r = np.asarray(rows, dtype=np.float32)
-        r = r.reshape(-1, r.shape[-1])
-        if r.shape[1] != self.n_win:
-            if r.shape[1] != self.row_length:
-                raise ValueError("rows must be n_win or row_length wide")
-            full = np.full((r.shape[0], self.n_win), np.nan, dtype=np.float32)  # the tail is never read
-            full[:, :r.shape[1]] = r
-            r = full
-        return np.ascontiguousarray(r)
-
     def viewport_push(self, rows) -> None:
         """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row),
         reduced into the viewport; synchronous."""
-        r = self._full_rows(rows)
+        r = full_rows(rows, self.n_win, self.row_length)
         check(self.lib.zfft_viewport_push(self._plan, r.ctypes.data_as(ctypes.c_void_p), r.shape[0]),
               "zfft_viewport_push")
 
@@ -726,7 +707,7 @@ class ZoomFFT:
         if rows is None:
             count, ptr = 0, None
         else:
-            r = self._full_rows(rows)
+            r = full_rows(rows, self.n_win, self.row_length)
             count, ptr = r.shape[0], r.ctypes.data
         check(self.lib.zfft_viewport_push_render(self._plan, ptr, count, out.ctypes.data), "zfft_viewport_push_render")
         return out
@@ -754,7 +735,7 @@ class ZoomFFT:
     def history_push(self, rows) -> None:
         """Host rows, (count, n_win) or (count, row_length) as `rows()` crops them (or one row),
         appended to the store; synchronous."""
-        r = self._full_rows(rows)
+        r = full_rows(rows, self.n_win, self.row_length)
         check(self.lib.zfft_history_push(self._plan, r.ctypes.data_as(ctypes.c_void_p), r.shape[0]),
               "zfft_history_push")
 

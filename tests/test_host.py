@@ -127,6 +127,32 @@ def test_window_refusals_follow_scipy(zfft_lib):
     assert kind == 100 and arr.dtype == np.float32
 
 
+def test_full_rows_normalises_host_rows():
+    """What every host-rows call passes on: C-contiguous float32 (count, n_win), the values kept;
+    row_length-wide rows get a NaN tail; any other width is refused."""
+    from pypanadapter_amd.engine import full_rows
+    n_win, row_length = 9, 6
+    one = full_rows(np.arange(n_win, dtype=np.float32), n_win, row_length)
+    assert one.shape == (1, n_win) and one.dtype == np.float32
+    np.testing.assert_array_equal(one[0], np.arange(n_win))
+    wide = np.arange(3 * n_win, dtype=np.float64).reshape(3, n_win) / 4.0  # exact in float32
+    r = full_rows(wide, n_win, row_length)
+    assert r.shape == (3, n_win) and r.dtype == np.float32 and r.flags.c_contiguous
+    np.testing.assert_array_equal(r, wide)
+    cropped = full_rows(wide[:, :row_length], n_win, row_length)
+    assert cropped.shape == (3, n_win) and cropped.dtype == np.float32 and cropped.flags.c_contiguous
+    np.testing.assert_array_equal(cropped[:, :row_length], wide[:, :row_length])
+    assert np.isnan(cropped[:, row_length:]).all()
+    strided = np.arange(6 * n_win, dtype=np.float32).reshape(6, n_win)[::2]
+    assert not strided.flags.c_contiguous
+    r = full_rows(strided, n_win, row_length)
+    assert r.flags.c_contiguous
+    np.testing.assert_array_equal(r, strided)
+    for bad in (n_win + 1, row_length - 1):
+        with pytest.raises(ValueError):
+            full_rows(np.zeros((2, bad), dtype=np.float32), n_win, row_length)
+
+
 def test_filter_constants_pinned_to_scipy():
     import json
     import scipy.signal as ss
