@@ -727,6 +727,75 @@ int zfft_history_reset(zfft_plan *plan); /* rows_seen and oldest back to 0 */
 int zfft_history_codes(int32_t format, double db_min, double db_max, const float *v, int64_t n, uint16_t *codes_out);
 int zfft_history_values(int32_t format, double db_min, double db_max, const uint16_t *codes, int64_t n, float *v_out);
 
+/* Channel taps: narrowband complex streams out of the wideband input.  A tap is a digital
+ * down-converter with state -- an oscillator, a real FIR low-pass, an integer decimation -- on the
+ * samples the plan is given, not on its rows; a plan holds up to max_taps of them, and one push of
+ * a contiguous stretch of input makes every open tap emit the output samples that fall in it.  The
+ * state between pushes stays on the device.  Off by default: a plan that never calls
+ * zfft_plan_taps allocates and launches nothing.  The rule (reference: tests/tap_ref.py):
+ *   1. samples: the plan counts input samples n = 0, 1, ... from zfft_plan_taps, or from
+ *      zfft_tap_reset(plan, n0), which restarts the count at n0 (0 <= n0 <= 2^62), zeroes the
+ *      carry and leaves the open taps open as if opened at n0.  x[n] is the input as the plan's
+ *      in_dtype loader defines it in float32 (all four in_dtype values), and x[n] = 0 for the
+ *      samples before the start.  flip_input = 1 has no continuous time axis: zfft_plan_taps
+ *      returns ZFFT_EUNSUPPORTED.
+ *   2. a tap has freq_word fw, an integer in [-2^31, 2^31): its centre frequency is fw / 2^32
+ *      cycles per input sample; decim D in [1, 512]; n_taps T in [1, max_len] (max_len <= 2048)
+ *      real float32 taps h[0 .. T); n_open, the count at which it was opened.
+ *   3. outputs: y[m] = sum_{k < T} h[k] x[m D - k] exp(-2 pi i ((fw (m D - k)) mod 2^32) / 2^32)
+ *      for every m with m D >= n_open.  The phase is integer arithmetic on the plan-wide count:
+ *      taps opened at different times are phase-coherent with each other, and nothing drifts or
+ *      loses precision with time (the phase wraps exactly; the count is 64-bit).
+ *   4. a push of n_samples at count n0 emits, per tap, the m with max(n0, n_open) <= m D <
+ *      n0 + n_samples: ceil((n0 + n_samples) / D) - ceil(max(n0, n_open) / D) samples
+ *      (zfft_tap_counts, for the next push).  The push writes complex64 outputs into one buffer,
+ *      the open taps in slot order back to back.  The outputs do not depend on how the stream is
+ *      cut into pushes, bit for bit.
+ *   5. a newly opened tap sees the true past: the plan carries the last max_len - 1 input samples
+ *      as complex64 whether or not any tap is open.
+ *   6. the group delay (T - 1) / 2 input samples is reported (zfft_tap_info), not compensated.
+ *   7. arithmetic, the form the FC decimator uses for its LO: c[k] = float32(h[k] exp(+2 pi i
+ *      ((fw k) mod 2^32) / 2^32)), built on the host in float64 (zfft_tap_table); y[m] = rot(m)
+ *      sum_k c[k] x[m D - k] with rot(m) = exp(-2 pi i ((fw m D) mod 2^32) / 2^32), one rotation
+ *      per output, in float32.  The sum's order is fixed: four partial sums a_j over the k = j
+ *      (mod 4) in ascending k, each step two fused multiply-adds per component (re: a.re + c.re
+ *      x.re, then - c.im x.im; im: a.im + c.re x.im, then + c.im x.re), then (a_0 + a_1) + (a_2 +
+ *      a_3).  |y - y_exact| <= (T + 32) 2^-24 sum|h| max|x|.
+ * zfft_tap_push_device is enqueued on its stream with no sync, ordered after earlier work on that
+ * stream and after the plan's earlier calls on any stream; d_out must hold the sum of
+ * zfft_tap_counts and overlap neither d_iq nor itself across taps.  zfft_tap_open uploads the
+ * tap's table on the plan's stream behind the enqueued pushes (it waits on the host only when the
+ * same slot is opened again while the plan's enqueued work, its last upload included, is still pending); zfft_tap_close is host
+ * bookkeeping.  Every zfft_tap_* call on a plan with taps off returns ZFFT_EINVAL (zfft_tap_shape
+ * after reporting 0, 0).  With zfft_plan_timing on a push reports its launch as "tap_push". */
+/* max_taps = max_len = 0: off, frees everything.  Otherwise max_taps in [1, 64], max_len in
+ * [1, 2048]; anything else ZFFT_EINVAL.  A call closes every tap and restarts the count at 0. */
+int zfft_plan_taps(zfft_plan *plan, int32_t max_taps, int32_t max_len);
+int zfft_tap_shape(const zfft_plan *plan, int32_t *max_taps, int32_t *max_len);
+/* h: n_taps host floats.  Opening an open slot replaces its tap (n_open = the count now). */
+int zfft_tap_open(zfft_plan *plan, int32_t slot, int64_t freq_word, int32_t decim, int32_t n_taps, const float *h);
+int zfft_tap_close(zfft_plan *plan, int32_t slot); /* ZFFT_EINVAL if the slot is not open */
+/* a closed slot reports is_open 0 and zeros; group_delay = (n_taps - 1) / 2 input samples */
+int zfft_tap_info(const zfft_plan *plan, int32_t slot, int32_t *is_open, int64_t *freq_word, int32_t *decim,
+                  int32_t *n_taps, uint64_t *n_open, double *group_delay);
+/* counts[max_taps]: what a push of n_samples (0 .. 2^31 - 1) now would emit per slot (closed: 0);
+ * a pure host function of the plan's count and its open taps */
+int zfft_tap_counts(const zfft_plan *plan, int64_t n_samples, int64_t *counts);
+/* n_samples (1 .. 2^31 - 1; 0 is ZFFT_OK and does nothing) samples of the plan's in_dtype on the
+ * device; `stream` is a hipStream_t like every hip_stream of this header (its ordering case, behind
+ * a stalled stream, is in tests/test_gpu_tap.py) */
+int zfft_tap_push_device(zfft_plan *plan, const void *d_iq, int64_t n_samples, void *d_out, void *stream);
+/* host samples and outputs; counts_out[max_taps] (or NULL) as zfft_tap_counts before the push; synchronous */
+int zfft_tap_push(zfft_plan *plan, const void *iq, int64_t n_samples, void *out, int64_t *counts_out);
+int zfft_tap_state(zfft_plan *plan, uint64_t *samples_seen);
+int zfft_tap_reset(zfft_plan *plan, int64_t n0);
+/* No plan, no GPU.  A Kaiser-windowed sinc in float64 normalised to unit gain at DC, cutoff in
+ * cycles per input sample (0 < cutoff < 0.5), n_taps in [1, 2048], beta >= 0:
+ * scipy.signal.firwin(n_taps, 2 cutoff, window=("kaiser", beta)). */
+int zfft_tap_design(int32_t n_taps, double cutoff, double beta, double *h_out);
+/* No plan, no GPU.  Rule 7's c[k] as n_taps interleaved (re, im) float32 pairs. */
+int zfft_tap_table(int64_t freq_word, int32_t n_taps, const float *h, float *c_out);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

@@ -94,6 +94,9 @@ EXPORTS = [
     "zfft_history_state", "zfft_history_read_device", "zfft_history_read", "zfft_history_view_device",
     "zfft_history_view", "zfft_history_render", "zfft_history_replay_viewport", "zfft_history_reset",
     "zfft_history_codes", "zfft_history_values",
+    "zfft_plan_taps", "zfft_tap_shape", "zfft_tap_open", "zfft_tap_close", "zfft_tap_info", "zfft_tap_counts",
+    "zfft_tap_push_device", "zfft_tap_push", "zfft_tap_state", "zfft_tap_reset", "zfft_tap_design",
+    "zfft_tap_table",
 ]
 
 _lib = None
@@ -227,6 +230,19 @@ def load(path: str = ""):
         "zfft_history_reset": (ctypes.c_int, [P]),
         "zfft_history_codes": (ctypes.c_int, [I32, D, D, P, I64, P]),
         "zfft_history_values": (ctypes.c_int, [I32, D, D, P, I64, P]),
+        "zfft_plan_taps": (ctypes.c_int, [P, I32, I32]),
+        "zfft_tap_shape": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+        "zfft_tap_open": (ctypes.c_int, [P, I32, I64, I32, I32, P]),
+        "zfft_tap_close": (ctypes.c_int, [P, I32]),
+        "zfft_tap_info": (ctypes.c_int, [P, I32, ctypes.POINTER(I32), ctypes.POINTER(I64), ctypes.POINTER(I32),
+                                          ctypes.POINTER(I32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(D)]),
+        "zfft_tap_counts": (ctypes.c_int, [P, I64, P]),
+        "zfft_tap_push_device": (ctypes.c_int, [P, P, I64, P, P]),
+        "zfft_tap_push": (ctypes.c_int, [P, P, I64, P, P]),
+        "zfft_tap_state": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_uint64)]),
+        "zfft_tap_reset": (ctypes.c_int, [P, I64]),
+        "zfft_tap_design": (ctypes.c_int, [I32, D, D, P]),
+        "zfft_tap_table": (ctypes.c_int, [I64, I32, P, P]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

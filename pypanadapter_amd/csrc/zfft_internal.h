@@ -1,9 +1,9 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
 // zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp,
-// zfft_history.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
+// zfft_history.cpp, zfft_tap.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
 // (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, fc2_kernels.hip,
 // detect_kernels.hip, detect_local_kernels.hip, track_kernels.hip, view_kernels.hip,
-// history_kernels.hip).  Not part of the C-ABI.
+// history_kernels.hip, tap_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 
 #include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
 #include "zfft_history_plan.h"  // the row history's quantiser and forms (HistQuant, HistForm)
+#include "zfft_tap_plan.h"     // the channel taps' forms and items (TapForm, TapItems)
 #include "zfft_track_plan.h"   // the emission tracker's forms and carried records (TrackForm, TrackOpen)
 #include "zfft_view_plan.h"    // the viewport's forms (ViewForm)
 #include "zfft_welch_plan.h"  // the Welch forms' domains (kMaxLdsFft, kDifMin / kDifMax, ...), WelchSel
@@ -515,6 +516,14 @@ hipError_t launch_history_view(const HistStore &s, const HistGeom &g, const Hist
                                size_t scratch_bytes, hipStream_t st);
 hipError_t launch_history_finish(const HistStore &s, const HistGeom &g, const HistForm &f, float *img,
                                  const void *scratch, size_t scratch_bytes, hipStream_t st);
+// Channel taps (zfft.h's rule of zfft_plan_taps; tap_kernels.hip): one push of n samples of `in`
+// (one of the InDtype formats, not flipped) as choose_tap cut it.  tab holds a row of max_len
+// entries c[k] per slot; carry_old the max_len - 1 samples before the push, carry_new those before
+// the next (two buffers: the first workgroups read the one while the last write the other); out
+// the items' outputs back to back.  in, out and the carries do not overlap.
+hipError_t launch_tap_push(const void *in, int dtype, int64_t n, int max_len, const TapForm &f, const TapItems &items,
+                           const float2 *tab, const float2 *carry_old, float2 *carry_new, float2 *out,
+                           hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

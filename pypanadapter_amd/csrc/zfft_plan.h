@@ -1,6 +1,7 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
-// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp).  Not part of the C-ABI.
+// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_tap.cpp).  Not part of
+// the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -161,6 +162,25 @@ struct zfft_plan {
   uint64_t hs_seen = 0;
   int hs_kind = 0;                 // HistForm::kind of the last view (test hook zfft__plan_history_form)
   DevBuf hs_store, hs_img, hs_rgba, hs_scratch, hs_replay;
+  // channel taps (zfft_plan_taps; zfft_tap.cpp): tp_max = max_taps, 0 = off (no buffer).  tp_tab
+  // holds a row of tp_len entries c[k] per slot, tp_carry two carries of tp_len - 1 samples (a
+  // push reads the one of parity tp_par and writes the other), tp_stage the device staging of
+  // zfft_tap_push, tp_pin the page-locked staging of the slots' table uploads (tp_dirty: a slot's
+  // part may still be read by an enqueued copy).  tp_n counts the samples given (host side:
+  // pushes are in call order), tp_slots the open taps
+  int tp_max = 0, tp_len = 0, tp_par = 0;
+  int tp_layout = 0;               // hook zfft__plan_tap_layout: 0 = the chooser's staging layout
+  uint64_t tp_n = 0;
+  struct TapSlot {
+    bool open = false;
+    int64_t fw = 0;
+    int32_t D = 0, T = 0;
+    uint64_t n_open = 0;
+  };
+  std::vector<TapSlot> tp_slots;
+  std::vector<char> tp_dirty;
+  DevBuf tp_tab, tp_carry, tp_stage;
+  float2 *tp_pin = nullptr;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the
@@ -245,6 +265,10 @@ int run_decimator(zfft_plan *p, const InDesc &in, int64_t L, int frames,
 void track_release(zfft_plan *p);
 // Everything of the tracker back to zero, in stream order; nothing while it is off.
 int track_restart(zfft_plan *p);
+
+// --- zfft_tap.cpp ---
+// Frees the channel taps and switches them off (the caller has waited for the plan's work).
+void tap_release(zfft_plan *p);
 
 // --- zfft_welch.cpp ---
 // The Welch rows (or lines) of `frames` decimated frames of Ld samples at x into d_rows, by the

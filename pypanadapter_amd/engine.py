@@ -612,6 +612,100 @@ class ZoomFFT:
     def track_reset(self) -> None:
         check(self.lib.zfft_track_reset(self._plan), "zfft_track_reset")
 
+    # ---------------------------------------------------------------- channel taps
+    def set_taps(self, max_taps: int, max_len: int = 2048) -> None:
+        """Channel taps (zfft_plan_taps): up to `max_taps` (at most 64) digital down-converters on
+        the plan's input samples, each an oscillator, a real FIR of at most `max_len` (at most
+        2048) taps and an integer decimation, with their state on the device from push to push.
+        The outputs do not depend on how the stream is cut into pushes, bit for bit.
+        set_taps(0, 0) turns them off and frees them.  A call closes every tap and restarts the
+        sample count.  The rule is in include/zfft.h, reproducible in numpy (tests/tap_ref.py)."""
+        check(self.lib.zfft_plan_taps(self._plan, int(max_taps), int(max_len)), "zfft_plan_taps")
+        self._tap_open = set()  # the open slots, mirrored here: a push asks the library once, not per slot
+
+    def tap_shape(self):
+        """(max_taps, max_len)."""
+        m, n = ctypes.c_int32(), ctypes.c_int32()
+        check(self.lib.zfft_tap_shape(self._plan, ctypes.byref(m), ctypes.byref(n)), "zfft_tap_shape")
+        return m.value, n.value
+
+    def tap_freq_word(self, f_hz: float) -> int:
+        """The freq_word nearest f_hz: round(f_hz / fs * 2^32), wrapped into [-2^31, 2^31)."""
+        return (int(round(float(f_hz) / self.fs * 2.0 ** 32)) + 2 ** 31) % 2 ** 32 - 2 ** 31
+
+    def tap_open(self, slot: int, f_hz: float, decim: int, taps=None, cutoff: float | None = None,
+                 beta: float = 8.0) -> float:
+        """Open (or replace) the tap in `slot` at centre frequency f_hz, decimating by `decim`
+        (1 .. 512); returns the frequency actually used (a multiple of fs / 2^32).  taps: real
+        FIR taps at the input rate; None designs a Kaiser-windowed sinc (`tap_design`) of
+        min(8 decim + 1, max_len) taps, `cutoff` cycles per input sample (default 0.4 / decim)
+        and `beta`.  The tap's first output is the first multiple of decim at or after the
+        samples pushed so far, and it sees the input before that."""
+        decim = int(decim)
+        if taps is None:
+            taps = tap_design(min(8 * decim + 1, self.tap_shape()[1]), 0.4 / decim if cutoff is None else cutoff, beta)
+        h = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        fw = self.tap_freq_word(f_hz)
+        check(self.lib.zfft_tap_open(self._plan, int(slot), fw, decim, h.size, h.ctypes.data_as(ctypes.c_void_p)),
+              "zfft_tap_open")
+        self._tap_open.add(int(slot))
+        return fw * self.fs / 2.0 ** 32
+
+    def tap_close(self, slot: int) -> None:
+        check(self.lib.zfft_tap_close(self._plan, int(slot)), "zfft_tap_close")
+        self._tap_open.discard(int(slot))
+
+    def tap_open_slots(self) -> list:
+        """The open slots in ascending order: the order of `tap_push`'s arrays."""
+        self.tap_shape()  # (ValueError while the taps are off)
+        return sorted(self._tap_open)
+
+    def tap_info(self, slot: int) -> dict:
+        """open, freq_word, f_hz, decim, n_taps, n_open (the sample count at which it was opened)
+        and group_delay ((n_taps - 1) / 2 input samples: reported, not compensated)."""
+        o, d, t = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        fw, n0, gd = ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_double()
+        check(self.lib.zfft_tap_info(self._plan, int(slot), ctypes.byref(o), ctypes.byref(fw), ctypes.byref(d),
+                                     ctypes.byref(t), ctypes.byref(n0), ctypes.byref(gd)), "zfft_tap_info")
+        return {"open": bool(o.value), "freq_word": fw.value, "f_hz": fw.value * self.fs / 2.0 ** 32,
+                "decim": d.value, "n_taps": t.value, "n_open": n0.value, "group_delay": gd.value}
+
+    def tap_counts(self, n: int) -> np.ndarray:
+        """Output samples per slot (closed: 0) of a push of n samples now; int64, max_taps long."""
+        out = np.zeros(self.tap_shape()[0], dtype=np.int64)
+        check(self.lib.zfft_tap_counts(self._plan, int(n), out.ctypes.data_as(ctypes.c_void_p)), "zfft_tap_counts")
+        return out
+
+    def tap_push(self, x) -> list:
+        """The next samples of the stream (1-D, the plan's input format) from the host; returns
+        one complex64 array per open slot, in slot order.  Synchronous."""
+        x = self._as_iq(x)
+        if x.ndim != 1:
+            raise ValueError("tap_push takes a 1-D stretch of samples")
+        n = self._samples(x)
+        counts = self.tap_counts(n)
+        out = np.empty(int(counts.sum()), dtype=np.complex64)
+        check(self.lib.zfft_tap_push(self._plan, x.ctypes.data_as(ctypes.c_void_p), n,
+                                     out.ctypes.data_as(ctypes.c_void_p), None), "zfft_tap_push")
+        ends = np.cumsum(counts)
+        return [out[ends[s] - counts[s]:ends[s]] for s in sorted(self._tap_open)]
+
+    def tap_push_device(self, d_iq_ptr: int, n: int, d_out_ptr: int, stream: int = 0) -> None:
+        """n samples on the device; the outputs (sum of tap_counts(n) complex64, the open taps in
+        slot order back to back) into d_out_ptr; enqueued on `stream`, no sync."""
+        check(self.lib.zfft_tap_push_device(self._plan, ctypes.c_void_p(d_iq_ptr), int(n), ctypes.c_void_p(d_out_ptr),
+                                            ctypes.c_void_p(stream or None)), "zfft_tap_push_device")
+
+    def tap_state(self) -> int:
+        """The input samples counted so far."""
+        v = ctypes.c_uint64()
+        check(self.lib.zfft_tap_state(self._plan, ctypes.byref(v)), "zfft_tap_state")
+        return v.value
+
+    def tap_reset(self, n0: int = 0) -> None:
+        """Restart the sample count at n0 with an all-zero past; open taps stay open."""
+        check(self.lib.zfft_tap_reset(self._plan, int(n0)), "zfft_tap_reset")
+
     # ---------------------------------------------------------------- display viewport
     def set_viewport(self, height: int, width: int, col0: int = 0, col1: int | None = None,
                      detector: str = "max", rows_per_line: int = 1) -> None:
@@ -958,6 +1052,25 @@ def native_window(window, length: int) -> np.ndarray:
     p = (ctypes.c_double * 2)(*params)
     check(lib.zfft_window_values(kind, p, int(length), out.ctypes.data_as(ctypes.c_void_p)),
           "zfft_window_values")
+    return out
+
+
+def tap_design(n_taps: int, cutoff: float, beta: float = 8.0) -> np.ndarray:
+    """A tap's default low-pass (zfft_tap_design; no GPU needed): a Kaiser-windowed sinc in
+    float64 with unit gain at DC, `cutoff` in cycles per input sample --
+    scipy.signal.firwin(n_taps, 2 * cutoff, window=("kaiser", beta))."""
+    out = np.empty(int(n_taps), dtype=np.float64)
+    check(_lib.load().zfft_tap_design(int(n_taps), float(cutoff), float(beta), out.ctypes.data_as(ctypes.c_void_p)),
+          "zfft_tap_design")
+    return out
+
+
+def tap_table(freq_word: int, taps) -> np.ndarray:
+    """The modulated table c[k] a tap runs with (zfft_tap_table; no GPU needed), complex64."""
+    h = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+    out = np.empty(h.size, dtype=np.complex64)
+    check(_lib.load().zfft_tap_table(int(freq_word), h.size, h.ctypes.data_as(ctypes.c_void_p),
+                                     out.ctypes.data_as(ctypes.c_void_p)), "zfft_tap_table")
     return out
 
 

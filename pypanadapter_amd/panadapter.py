@@ -676,6 +676,83 @@ class History:
         return (centre - self.cols // 2) * (float(fs) / (int(zoom) * int(n_fft)))
 
 
+class Tap:
+    """Narrowband complex streams out of the wideband input, on the device (ZoomFFT.set_taps; the
+    rule is in include/zfft.h): every tap is an oscillator, a low-pass and an integer decimation
+    with its state kept from push to push, so the outputs are one continuous stream however the
+    input arrives.
+
+        taps = Tap(fs)                                   # for a caller of read_samples()
+        taps.open(0, 7.074e6 - f_centre, decim=128)      # a click on a carrier
+        ext = det.track_extent(det.open_tracks(), fs, N, zoom, line_period)
+        slot = taps.open_for(ext, 0)                     # ... or a track handed over
+        iq = taps.push(chunk)[slot]                      # complex64 at taps.rate(slot)
+
+    `push` takes the next stretch of samples (any length) and returns {slot: complex64 outputs}.
+    Frequencies are Hz in the samples' own baseband; the group delay (n_taps - 1) / 2 input
+    samples is reported by `info`, not compensated."""
+
+    def __init__(self, fs: float, max_taps: int = 8, max_len: int = 2048, in_dtype: str = "complex64",
+                 device: int = 0):
+        self.fs = float(fs)
+        self._plan = ZoomFFT(32, 1, self.fs, device=device, in_dtype=in_dtype)  # (the taps read samples, not rows)
+        self._plan.set_taps(max_taps, max_len)
+        self.max_taps, self.max_len = int(max_taps), int(max_len)
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+    def open(self, slot: int, f_hz: float, decim: int, taps=None, cutoff: float | None = None,
+             beta: float = 8.0) -> float:
+        """ZoomFFT.tap_open: returns the centre frequency actually used."""
+        return self._plan.tap_open(slot, f_hz, decim, taps=taps, cutoff=cutoff, beta=beta)
+
+    def open_for(self, extent: dict, index: int = 0, margin: float = 1.25, slot: int | None = None,
+                 centre: float = 0.0) -> int:
+        """Open a tap on entry `index` of `Detector.track_extent`: at the middle of the track's band
+        [f_lo, f_hi] (Hz from the rows' centre, which is `centre` Hz in the samples' baseband: 0 at
+        zoom 1, the plan's f_lo otherwise), with the largest decimation whose output rate
+        fs / decim is still at least `margin` times the band's width, and the default design.
+        Takes the first free slot unless `slot` is given; returns the slot."""
+        f_lo = float(np.atleast_1d(extent["f_lo"])[index])
+        f_hi = float(np.atleast_1d(extent["f_hi"])[index])
+        need = float(margin) * abs(f_hi - f_lo)
+        decim = 512 if need <= 0 else int(min(512, max(1, np.floor(self.fs / need))))
+        if slot is None:
+            free = sorted(set(range(self.max_taps)) - set(self._plan.tap_open_slots()))
+            if not free:
+                raise ValueError("every tap slot is open")
+            slot = free[0]
+        self.open(slot, centre + 0.5 * (f_lo + f_hi), decim)
+        return int(slot)
+
+    def close_tap(self, slot: int) -> None:
+        self._plan.tap_close(slot)
+
+    def info(self, slot: int) -> dict:
+        return self._plan.tap_info(slot)
+
+    def rate(self, slot: int) -> float:
+        """The tap's output rate fs / decim in Hz."""
+        return self.fs / self._plan.tap_info(slot)["decim"]
+
+    def counts(self, n: int) -> np.ndarray:
+        return self._plan.tap_counts(n)
+
+    def push(self, chunk) -> dict:
+        """{slot: complex64 outputs} of the open taps for the next samples of the stream."""
+        return dict(zip(self._plan.tap_open_slots(), self._plan.tap_push(chunk)))
+
+    @property
+    def samples_seen(self) -> int:
+        return self._plan.tap_state()
+
+    def reset(self, n0: int = 0) -> None:
+        self._plan.tap_reset(n0)
+
+
 class Data:
     """pypanadapter_thread.py's `Data` (T:1400-1483) on the pinned double-buffered IQRing
     (SURVEY §8f-1), same calls: the reader thread's `add(chunk)` (T:2191) and the PSD
