@@ -796,6 +796,72 @@ int zfft_tap_design(int32_t n_taps, double cutoff, double beta, double *h_out);
 /* No plan, no GPU.  Rule 7's c[k] as n_taps interleaved (re, im) float32 pairs. */
 int zfft_tap_table(int64_t freq_word, int32_t n_taps, const float *h, float *c_out);
 
+/* Channeliser: a polyphase-FFT bank of M uniform channels on the samples the plan is given.  Where
+ * a tap takes one signal out of the input, the bank takes every channel of the band at once: one
+ * prototype low-pass shared by all channels and one M-point transform per output step.  Off by
+ * default: a plan that never calls zfft_plan_chan allocates and launches nothing.  The rule
+ * (reference: tests/chan_ref.py):
+ *   1. samples: the plan counts input samples n = 0, 1, ... from zfft_plan_chan, or from
+ *      zfft_chan_reset(plan, n0), which restarts the count at n0 (0 <= n0 <= 2^62) and zeroes the
+ *      carry.  x[n] is the input as the plan's in_dtype loader defines it in float32 (all four
+ *      in_dtype values), and x[n] = 0 for the samples before the start.  flip_input = 1 has no
+ *      continuous time axis: zfft_plan_chan returns ZFFT_EUNSUPPORTED.  The count and the carry
+ *      are the channeliser's own, independent of the taps'; a caller who resets both to the same
+ *      n0 gets phase-coherent outputs from both.
+ *   2. shape: M channels, a power of two in [8, 1024]; P >= 1 taps per branch; T = M P <= 2048
+ *      real float32 prototype taps h[0 .. T); decimation D = M (critically sampled) or M / 2
+ *      (2x oversampled).
+ *   3. outputs: for every step m with m D >= the start and every channel c in [0, M),
+ *        y[m, c] = sum_{k < T} h[k] x[m D - k] exp(-2 pi i c (m D - k) / M),
+ *      which is a tap at freq_word c 2^32 / M, decimation D, taps h, on the same count.  Channels
+ *      c >= M / 2 are the negative frequencies.  Computed in the polyphase form: w_m[s] = sum of
+ *      h[k] x[m D - k] over the k with (m D - k) = s (mod M), k ascending -- P terms, each one
+ *      fused multiply-add per component from zero -- and y[m, .] = DFT_M(w_m), forward and
+ *      unnormalised.  The transform is indexed by the absolute sample index mod M: no per-step
+ *      rotation for either D.
+ *   4. a push of n_samples at count n0 emits the steps m with n0 <= m D < n0 + n_samples:
+ *      ceil((n0 + n_samples) / D) - ceil(n0 / D) of them (zfft_chan_steps, for the next push).
+ *      The outputs do not depend on how the stream is cut into pushes, bit for bit: the plan
+ *      carries the last T - 1 samples as the loader's float32 values, and the order of the FIR and
+ *      the transform are fixed functions of M, P and D.
+ *   5. selection: zfft_chan_select(plan, c_first, c_count) keeps the channels (c_first + i) mod M,
+ *      i < c_count, 1 <= c_count <= M; the default 0, M is all of them and M / 2, M is ascending
+ *      frequency.
+ *   6. layout: time-major complex64, out[j K + i] for step j of the push and kept channel i,
+ *      K = c_count; one channel's stream is the strided column.  Only kept channels are written,
+ *      and a kept channel's values are bit-identical whatever else is selected.
+ *   7. the group delay (T - 1) / 2 input samples is reported (zfft_chan_info), not compensated;
+ *      the output rate is fs / D.
+ *   8. |y - y_exact| <= (P + 5 log2 M + 2) 2^-24 sum|h| max|x|: P rounded multiply-adds per
+ *      branch, and per radix-2-equivalent level of the transform a complex multiply, a twiddle
+ *      rounded once from float64 and an add.
+ *   9. the default prototype is zfft_chan_design(M, P, beta) = zfft_tap_design(M P, 0.5 / M, beta):
+ *      a Kaiser sinc, -6 dB at the channel edge, unit gain at DC; beta = 8 where h is NULL.
+ * zfft_chan_push_device is enqueued on its stream with no sync, ordered after earlier work on that
+ * stream and after the plan's earlier calls on any stream; d_out must hold zfft_chan_steps x
+ * c_count complex64 and not overlap d_iq.  Every zfft_chan_* call on a plan with the channeliser
+ * off returns ZFFT_EINVAL ("channels are off"; zfft_chan_shape after reporting zeros).  With
+ * zfft_plan_timing on a push reports its one launch as "chan_push". */
+/* n_chan = 0: off, frees everything.  Otherwise n_chan, taps_per_chan, decim as rule 2, anything
+ * else ZFFT_EINVAL; h: n_chan taps_per_chan host floats, or NULL for rule 9's default.  A call
+ * restarts the count at 0 with all channels selected. */
+int zfft_plan_chan(zfft_plan *plan, int32_t n_chan, int32_t taps_per_chan, int32_t decim, const float *h);
+int zfft_chan_shape(const zfft_plan *plan, int32_t *n_chan, int32_t *taps_per_chan, int32_t *decim,
+                    int32_t *c_first, int32_t *c_count);
+int zfft_chan_select(zfft_plan *plan, int32_t c_first, int32_t c_count);
+/* the steps a push of n_samples (0 .. 2^31 - 1) now would emit; a pure host function of the count */
+int zfft_chan_steps(const zfft_plan *plan, int64_t n_samples, int64_t *steps);
+/* n_samples (1 .. 2^31 - 1; 0 is ZFFT_OK and does nothing) samples of the plan's in_dtype on the device */
+int zfft_chan_push_device(zfft_plan *plan, const void *d_iq, int64_t n_samples, void *d_out, void *stream);
+/* host samples and outputs; steps_out (or NULL) as zfft_chan_steps before the push; synchronous */
+int zfft_chan_push(zfft_plan *plan, const void *iq, int64_t n_samples, void *out, int64_t *steps_out);
+int zfft_chan_state(zfft_plan *plan, uint64_t *samples_seen);
+int zfft_chan_reset(zfft_plan *plan, int64_t n0);
+/* group_delay = (M P - 1) / 2 input samples; rate_ratio = 1 / D output samples per input sample */
+int zfft_chan_info(const zfft_plan *plan, double *group_delay, double *rate_ratio);
+/* No plan, no GPU.  Rule 9: n_chan taps_per_chan float64 values. */
+int zfft_chan_design(int32_t n_chan, int32_t taps_per_chan, double beta, double *h_out);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

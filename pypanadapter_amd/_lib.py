@@ -97,6 +97,8 @@ EXPORTS = [
     "zfft_plan_taps", "zfft_tap_shape", "zfft_tap_open", "zfft_tap_close", "zfft_tap_info", "zfft_tap_counts",
     "zfft_tap_push_device", "zfft_tap_push", "zfft_tap_state", "zfft_tap_reset", "zfft_tap_design",
     "zfft_tap_table",
+    "zfft_plan_chan", "zfft_chan_shape", "zfft_chan_select", "zfft_chan_steps", "zfft_chan_push_device",
+    "zfft_chan_push", "zfft_chan_state", "zfft_chan_reset", "zfft_chan_info", "zfft_chan_design",
 ]
 
 _lib = None
@@ -243,6 +245,16 @@ def load(path: str = ""):
         "zfft_tap_reset": (ctypes.c_int, [P, I64]),
         "zfft_tap_design": (ctypes.c_int, [I32, D, D, P]),
         "zfft_tap_table": (ctypes.c_int, [I64, I32, P, P]),
+        "zfft_plan_chan": (ctypes.c_int, [P, I32, I32, I32, P]),
+        "zfft_chan_shape": (ctypes.c_int, [P] + [ctypes.POINTER(I32)] * 5),
+        "zfft_chan_select": (ctypes.c_int, [P, I32, I32]),
+        "zfft_chan_steps": (ctypes.c_int, [P, I64, ctypes.POINTER(I64)]),
+        "zfft_chan_push_device": (ctypes.c_int, [P, P, I64, P, P]),
+        "zfft_chan_push": (ctypes.c_int, [P, P, I64, P, P]),
+        "zfft_chan_state": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_uint64)]),
+        "zfft_chan_reset": (ctypes.c_int, [P, I64]),
+        "zfft_chan_info": (ctypes.c_int, [P, ctypes.POINTER(D), ctypes.POINTER(D)]),
+        "zfft_chan_design": (ctypes.c_int, [I32, I32, D, P]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

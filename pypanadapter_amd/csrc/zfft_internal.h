@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "zfft_chan_plan.h"    // the channeliser's forms (ChanForm)
 #include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
 #include "zfft_history_plan.h"  // the row history's quantiser and forms (HistQuant, HistForm)
 #include "zfft_tap_plan.h"     // the channel taps' forms and items (TapForm, TapItems)
@@ -524,6 +525,13 @@ hipError_t launch_history_finish(const HistStore &s, const HistGeom &g, const Hi
 hipError_t launch_tap_push(const void *in, int dtype, int64_t n, int max_len, const TapForm &f, const TapItems &items,
                            const float2 *tab, const float2 *carry_old, float2 *carry_new, float2 *out,
                            hipStream_t st);
+// Channeliser (zfft.h's rule of zfft_plan_chan; chan_kernels.hip): one push of n samples of `in`
+// (one of the InDtype formats, not flipped) as choose_chan cut it for K kept channels from c_first.
+// h holds the M P prototype taps, tw chan_twiddles(M); carry_old the M P - 1 samples before the
+// push, carry_new those before the next; out[step * K + i].  in, out and the carries do not overlap.
+hipError_t launch_chan_push(const void *in, int dtype, int64_t n, int M, int P, int D, int c_first, int K,
+                            const ChanForm &f, const float *h, const float2 *tw, const float2 *carry_old,
+                            float2 *carry_new, float2 *out, hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

@@ -1,6 +1,6 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
-// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_tap.cpp).  Not part of
+// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_tap.cpp, zfft_chan.cpp).  Not part of
 // the C-ABI.
 #pragma once
 
@@ -14,6 +14,8 @@
 #include "zfft_internal.h"
 
 namespace zfft {
+
+struct ChanState;  // zfft_chan.cpp
 
 // A grow-only device buffer, freed with its owner.
 struct DevBuf {
@@ -181,6 +183,8 @@ struct zfft_plan {
   std::vector<char> tp_dirty;
   DevBuf tp_tab, tp_carry, tp_stage;
   float2 *tp_pin = nullptr;
+  // channeliser (zfft_plan_chan; zfft_chan.cpp): null = off (nothing allocated); the state is that file's
+  zfft::ChanState *chan = nullptr;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the
@@ -269,6 +273,10 @@ int track_restart(zfft_plan *p);
 // --- zfft_tap.cpp ---
 // Frees the channel taps and switches them off (the caller has waited for the plan's work).
 void tap_release(zfft_plan *p);
+
+// --- zfft_chan.cpp ---
+// Frees the channeliser and switches it off (the caller has waited for the plan's work).
+void chan_release(zfft_plan *p);
 
 // --- zfft_welch.cpp ---
 // The Welch rows (or lines) of `frames` decimated frames of Ld samples at x into d_rows, by the

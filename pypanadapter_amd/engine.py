@@ -706,6 +706,89 @@ class ZoomFFT:
         """Restart the sample count at n0 with an all-zero past; open taps stay open."""
         check(self.lib.zfft_tap_reset(self._plan, int(n0)), "zfft_tap_reset")
 
+    # ---------------------------------------------------------------- channeliser
+    def set_channels(self, n_chan: int, taps_per_channel: int = 8, oversample: int = 2, taps=None,
+                     beta: float = 8.0) -> None:
+        """Channeliser (zfft_plan_chan): a polyphase-FFT bank of `n_chan` uniform channels (a power
+        of two in [8, 1024]) on the input samples, every channel fs / n_chan wide between its -6 dB
+        edges and emitted at fs / decim, decim = n_chan / oversample (oversample 1 or 2).  taps:
+        n_chan * taps_per_channel real prototype taps at the input rate; None designs
+        `chan_design(n_chan, taps_per_channel, beta)`.  set_channels(0) turns it off and frees it.
+        A call restarts the sample count with all channels selected.  The rule is in
+        include/zfft.h, reproducible in numpy (tests/chan_ref.py)."""
+        if int(n_chan) == 0:
+            check(self.lib.zfft_plan_chan(self._plan, 0, 0, 0, None), "zfft_plan_chan")
+            return
+        if oversample not in (1, 2):
+            raise ValueError("oversample is 1 (critically sampled) or 2")
+        if taps is None:
+            taps = chan_design(n_chan, taps_per_channel, beta)
+        h = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        if h.size != int(n_chan) * int(taps_per_channel):
+            raise ValueError("taps: n_chan * taps_per_channel values")
+        check(self.lib.zfft_plan_chan(self._plan, int(n_chan), int(taps_per_channel), int(n_chan) // oversample,
+                                      h.ctypes.data_as(ctypes.c_void_p)), "zfft_plan_chan")
+
+    def chan_shape(self):
+        """(n_chan, taps_per_channel, decim, c_first, c_count)."""
+        v = [ctypes.c_int32() for _ in range(5)]
+        check(self.lib.zfft_chan_shape(self._plan, *[ctypes.byref(x) for x in v]), "zfft_chan_shape")
+        return tuple(x.value for x in v)
+
+    def chan_select(self, c_first: int, c_count: int) -> None:
+        """Keep the channels (c_first + i) mod n_chan, i < c_count: (0, n_chan) is all of them in
+        transform order, (n_chan / 2, n_chan) ascending frequency."""
+        check(self.lib.zfft_chan_select(self._plan, int(c_first), int(c_count)), "zfft_chan_select")
+
+    def chan_steps(self, n: int) -> int:
+        """Output steps of a push of n samples now."""
+        v = ctypes.c_int64()
+        check(self.lib.zfft_chan_steps(self._plan, int(n), ctypes.byref(v)), "zfft_chan_steps")
+        return v.value
+
+    def chan_push(self, x) -> np.ndarray:
+        """The next samples of the stream (1-D, the plan's input format) from the host; returns a
+        (steps, c_count) complex64 array, one row per output step.  Synchronous."""
+        x = self._as_iq(x)
+        if x.ndim != 1:
+            raise ValueError("chan_push takes a 1-D stretch of samples")
+        n = self._samples(x)
+        out = np.empty((self.chan_steps(n), self.chan_shape()[4]), dtype=np.complex64)
+        check(self.lib.zfft_chan_push(self._plan, x.ctypes.data_as(ctypes.c_void_p), n,
+                                      out.ctypes.data_as(ctypes.c_void_p), None), "zfft_chan_push")
+        return out
+
+    def chan_push_device(self, d_iq_ptr: int, n: int, d_out_ptr: int, stream: int = 0) -> None:
+        """n samples on the device; chan_steps(n) x c_count complex64 into d_out_ptr; enqueued on
+        `stream`, no sync."""
+        check(self.lib.zfft_chan_push_device(self._plan, ctypes.c_void_p(d_iq_ptr), int(n),
+                                             ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream or None)),
+              "zfft_chan_push_device")
+
+    def chan_state(self) -> int:
+        """The input samples counted so far."""
+        v = ctypes.c_uint64()
+        check(self.lib.zfft_chan_state(self._plan, ctypes.byref(v)), "zfft_chan_state")
+        return v.value
+
+    def chan_reset(self, n0: int = 0) -> None:
+        """Restart the sample count at n0 with an all-zero past; the shape and selection stay."""
+        check(self.lib.zfft_chan_reset(self._plan, int(n0)), "zfft_chan_reset")
+
+    def chan_info(self) -> dict:
+        """group_delay ((n_chan * taps_per_channel - 1) / 2 input samples: reported, not
+        compensated) and rate_ratio (output samples per input sample, 1 / decim)."""
+        gd, rr = ctypes.c_double(), ctypes.c_double()
+        check(self.lib.zfft_chan_info(self._plan, ctypes.byref(gd), ctypes.byref(rr)), "zfft_chan_info")
+        return {"group_delay": gd.value, "rate_ratio": rr.value}
+
+    def chan_freqs(self) -> np.ndarray:
+        """The centre of every kept channel in Hz in the samples' baseband (negative for the
+        channels from n_chan / 2 on), in the order of chan_push's columns."""
+        m, _, _, c0, k = self.chan_shape()
+        c = (c0 + np.arange(k)) % m
+        return np.where(c >= m // 2, c - m, c) * (self.fs / m)
+
     # ---------------------------------------------------------------- display viewport
     def set_viewport(self, height: int, width: int, col0: int = 0, col1: int | None = None,
                      detector: str = "max", rows_per_line: int = 1) -> None:
@@ -1062,6 +1145,16 @@ def tap_design(n_taps: int, cutoff: float, beta: float = 8.0) -> np.ndarray:
     out = np.empty(int(n_taps), dtype=np.float64)
     check(_lib.load().zfft_tap_design(int(n_taps), float(cutoff), float(beta), out.ctypes.data_as(ctypes.c_void_p)),
           "zfft_tap_design")
+    return out
+
+
+def chan_design(n_chan: int, taps_per_channel: int = 8, beta: float = 8.0) -> np.ndarray:
+    """The channeliser's default prototype (zfft_chan_design; no GPU needed):
+    tap_design(n_chan * taps_per_channel, 0.5 / n_chan, beta) -- -6 dB at the channel edge, unit
+    gain at DC."""
+    out = np.empty(int(n_chan) * int(taps_per_channel), dtype=np.float64)
+    check(_lib.load().zfft_chan_design(int(n_chan), int(taps_per_channel), float(beta),
+                                       out.ctypes.data_as(ctypes.c_void_p)), "zfft_chan_design")
     return out
 
 

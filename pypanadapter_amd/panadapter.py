@@ -753,6 +753,83 @@ class Tap:
         self._plan.tap_reset(n0)
 
 
+class Channelizer:
+    """Every channel of the band at once, on the device (ZoomFFT.set_channels; the rule is in
+    include/zfft.h): a polyphase-FFT bank of `n_chan` uniform channels with its state kept from
+    push to push, so each column is one continuous narrowband stream however the input arrives.
+
+        bank = Channelizer(fs, 64)                       # for a caller of read_samples()
+        y = bank.push(chunk)                             # (steps, 64) complex64 at bank.rate
+        ext = det.track_extent(det.open_tracks(), fs, N, zoom, line_period)
+        iq = y[:, bank.channel_for(ext, 0)]              # the channel a track lies in
+
+    Columns are in ascending frequency (`freqs`, Hz in the samples' own baseband) unless
+    `ascending=False` keeps the transform's order.  The group delay is reported, not compensated."""
+
+    def __init__(self, fs: float, n_chan: int, taps_per_channel: int = 8, oversample: int = 2, taps=None,
+                 beta: float = 8.0, in_dtype: str = "complex64", ascending: bool = True, device: int = 0):
+        self.fs = float(fs)
+        self._plan = ZoomFFT(32, 1, self.fs, device=device, in_dtype=in_dtype)  # (the bank reads samples, not rows)
+        self._plan.set_channels(n_chan, taps_per_channel, oversample, taps=taps, beta=beta)
+        self.n_chan = int(n_chan)
+        if ascending:
+            self._plan.chan_select(self.n_chan // 2, self.n_chan)
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+    def select(self, c_first: int, c_count: int) -> None:
+        self._plan.chan_select(c_first, c_count)
+
+    @property
+    def freqs(self) -> np.ndarray:
+        """The centre of every kept channel in Hz, in the order of `push`'s columns."""
+        return self._plan.chan_freqs()
+
+    @property
+    def rate(self) -> float:
+        """The channels' output rate fs / decim in Hz."""
+        return self.fs * self._plan.chan_info()["rate_ratio"]
+
+    @property
+    def group_delay(self) -> float:
+        """(n_chan * taps_per_channel - 1) / 2 input samples."""
+        return self._plan.chan_info()["group_delay"]
+
+    def steps(self, n: int) -> int:
+        return self._plan.chan_steps(n)
+
+    def push(self, chunk) -> np.ndarray:
+        """(steps, kept channels) complex64 for the next samples of the stream."""
+        return self._plan.chan_push(chunk)
+
+    def channel_of(self, f_hz: float) -> int:
+        """The column of `push` whose channel covers f_hz (Hz in the samples' baseband, taken
+        modulo fs); ValueError when that channel is not kept."""
+        _, _, _, c0, k = self._plan.chan_shape()
+        c = int(np.floor(float(f_hz) / self.fs * self.n_chan + 0.5)) % self.n_chan
+        i = (c - c0) % self.n_chan
+        if i >= k:
+            raise ValueError(f"channel {c} is not among the kept channels")
+        return i
+
+    def channel_for(self, extent: dict, index: int = 0, centre: float = 0.0) -> int:
+        """The column covering the middle of entry `index` of `Detector.track_extent` (its band
+        [f_lo, f_hi] in Hz from the rows' centre, which is `centre` Hz in the samples' baseband)."""
+        f_lo = float(np.atleast_1d(extent["f_lo"])[index])
+        f_hi = float(np.atleast_1d(extent["f_hi"])[index])
+        return self.channel_of(centre + 0.5 * (f_lo + f_hi))
+
+    @property
+    def samples_seen(self) -> int:
+        return self._plan.chan_state()
+
+    def reset(self, n0: int = 0) -> None:
+        self._plan.chan_reset(n0)
+
+
 class Data:
     """pypanadapter_thread.py's `Data` (T:1400-1483) on the pinned double-buffered IQRing
     (SURVEY §8f-1), same calls: the reader thread's `add(chunk)` (T:2191) and the PSD
