@@ -21,6 +21,7 @@
 
 #include "zfft_device.h"
 #include "zfft_fft.h"
+#include "zfft_dif_addr.h"
 
 namespace zfft {
 
@@ -425,13 +426,58 @@ __global__ __launch_bounds__(256) void ingest_kernel(InDesc in, const v2f *__res
 }
 
 // ------------------------------------------------------------------ Welch row
+// Sum over the 64 lanes of a wave, pairing as the xor butterfly 32, 16, 8, 4, 2, 1 does; LANE 0
+// HOLDS THE TOTAL (every caller reads lane 0 alone).  The exchanges stay in the VALU
+// (tests/test_welch_lane_sum.py models this sequence): v_permlane32_swap / v_permlane16_swap of
+// the value with a copy of itself give every lane its partner across the halves and across the
+// row pairs; inside a 16-lane row the partner comes through DPP operands of the add itself --
+// row_ror:8 (xor 8), row_shl:4 (lane i takes i + 4: right for the lanes with bit 2 clear, where
+// lane 0's operands live; a lane without a source adds 0), quad_perm 2,3,0,1 and 1,0,3,2 (xor 2
+// and 1).  Float addition commutes, so lane 0's bits are those of the butterfly.
+#ifndef ZFFT_WSUM_DPP
+#define ZFFT_WSUM_DPP 1  // 0: __shfl_xor (ds_bpermute_b32, a round trip through the LDS pipe per step)
+#endif
+template <int CTRL>
+__device__ __forceinline__ float dpp_get(float f) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0u, __builtin_bit_cast(unsigned, f), CTRL, 0xf, 0xf, true));
+}
+// f + (f of the partner lane across the wave's halves, W = 32, or across a pair of rows, W = 16).
+// The swap of a value with its own copy leaves the lower partner's value in every lane of one
+// result and the upper partner's in the other.  (The results go through by-value helpers:
+// __builtin_bit_cast applied to element 1 of the result vector read element 0 -- it added the first
+// result to itself, a wrong mean on the device -- as fc_kernels.hip notes for its fbits.)
+__device__ __forceinline__ float wsum_f(unsigned u) { return __builtin_bit_cast(float, u); }
+template <int W>
+__device__ __forceinline__ float swap_add(float f) {
+  const unsigned u = __builtin_bit_cast(unsigned, f);
+  if constexpr (W == 32) {
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    const unsigned r0 = r[0], r1 = r[1];
+    return wsum_f(r0) + wsum_f(r1);
+  } else {
+    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    const unsigned r0 = r[0], r1 = r[1];
+    return wsum_f(r0) + wsum_f(r1);
+  }
+}
 __device__ __forceinline__ v2f wave_sum(v2f v) {
+#if ZFFT_WSUM_DPP
+  float sx = v.x, sy = v.y;
+  sx = swap_add<32>(sx), sy = swap_add<32>(sy);
+  sx = swap_add<16>(sx), sy = swap_add<16>(sy);
+  sx += dpp_get<0x128>(sx), sy += dpp_get<0x128>(sy);  // row_ror:8
+  sx += dpp_get<0x104>(sx), sy += dpp_get<0x104>(sy);  // row_shl:4
+  sx += dpp_get<0x4e>(sx), sy += dpp_get<0x4e>(sy);    // quad_perm:[2,3,0,1]
+  sx += dpp_get<0xb1>(sx), sy += dpp_get<0xb1>(sy);    // quad_perm:[1,0,3,2]
+  return v2f{sx, sy};
+#else
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
     v.x += __shfl_xor(v.x, m, 64);
     v.y += __shfl_xor(v.y, m, 64);
   }
   return v;
+#endif
 }
 
 // Row slot of bin k (-1: cropped) and its one-sided factor.  Two-sided: fftshift + crop,
@@ -673,7 +719,11 @@ constexpr int kDifPfSmallPrune = 4;    // prefetch of that form (fits 128 VGPRs)
 #endif
 constexpr int kDifPf16k = ZFFT_DIF_PF16K;  // N = 16384 (PRUNE; the full form: none): one
                                             // 1024-thread frame, 4 waves/SIMD (128 VGPRs)
-__host__ __device__ constexpr int dif_slot(int i) { return i + (i >> 4); }  // conflict-free strides 1, 16, 17
+// Register and address plans of this round (zfft_dif_addr.h; measured: profiles/welch_regs):
+//   ZFFT_DIF_CADDR  one LDS base per stage and segment, constant offsets per value
+//   ZFFT_DIF_WHOLD  the window held in registers where the launch bound leaves room (win_hold)
+//   ZFFT_DIF_PFPIN  the next segment's prefetch requested and pinned at the segment head
+__host__ __device__ constexpr int dif_slot(int i) { return zfft::dif::slot(i); }
 
 template <int N>
 struct Dif {
@@ -720,6 +770,12 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
                       WelchLines ln) {
   using D = Dif<N>;
   constexpr int T = D::T, PF = PRUNE ? D::PF_PRUNE : D::PF;
+  // n_fft is N by the launcher's switch: said here, the pruned forms' row-slot arithmetic folds to
+  // constants (a scalar register less in the line writer; the full forms are better off without)
+  if constexpr (ZFFT_DIF_CADDR && PRUNE) g.n_fft = N;
+  // stage 2's twiddle bases are held like stage 1's, except where the 128 registers of the
+  // 1024-thread frame do not hold them beside the line bookkeeping: re-read per segment there
+  constexpr bool HB2 = ZFFT_DIF_CADDR ? !(N == 16384 && LINES) : true;
   extern __shared__ v2f dyn_sh[];
   __shared__ v2f red[D::FPB][2][D::NW];  // wave partial sums of the segment mean, by parity
   const int fl = D::FPB == 1 ? 0 : (int)threadIdx.x / T;  // frame within the workgroup
@@ -750,7 +806,7 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       b1[i] = base_of(1, t, i);
-      b2[i] = D::PM >= 2 ? base_of(2, t, i) : splat(0.f);
+      b2[i] = D::PM >= 2 && HB2 ? base_of(2, t, i) : splat(0.f);
     }
   }
 #if ZFFT_DIF_BUF
@@ -799,6 +855,12 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
   const int per = LINES ? lpp * ln.grp : (g.nseg + g.split - 1) / g.split;
   const int s0 = (int)blockIdx.y * per, s1 = min(g.nseg, s0 + per);
   int line = (int)blockIdx.y * lpp, left = LINES ? min(ln.grp, g.nseg - s0) : 0;
+  // window values held across the segments (the same for every segment: loaded once)
+  constexpr int WH = zfft::dif::win_hold(N, PRUNE, HALF, SEG, LINES);
+  float wh[WH > 0 ? WH : 1];
+  (void)wh;
+#pragma unroll
+  for (int r = 0; r < WH; ++r) wh[r] = DIF_W((int)threadIdx.x % T, r);
   load_seg(pfa, s0, threadIdx.x % T);
   post_sum(pfa, s0 & 1, s0, threadIdx.x % T);
   sync();
@@ -815,19 +877,22 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       asm volatile("" : "+v"(b1[i]));
-      asm volatile("" : "+v"(b2[i]));
+      if constexpr (HB2) asm volatile("" : "+v"(b2[i]));
     }
     v2f v[16];
     {  // values [0, PF) were prefetched a segment ahead, the rest load now
 #pragma unroll
       for (int r = 0; r < 16; ++r) v[r] = r < PF ? pf[r] : DIF_X(s, t, r);
     }
-    // the window values requested before the next segment's prefetch: the wait for them (the
-    // vector-memory counter completes in order) then leaves the prefetch in flight (requested
-    // after it, every segment drained its own prefetch right away)
+    // The window: WH values are held in registers for the whole kernel (win_hold), the others
+    // are requested here, before the next segment's prefetch, so that the wait for them (the
+    // vector-memory counter completes in order) leaves the prefetch in flight.  (With none held
+    // and the prefetch left to the compiler -- ZFFT_DIF_WHOLD=0, ZFFT_DIF_PFPIN=0 -- the 16
+    // window loads are waited down to vmcnt(0) before the first butterfly with nothing behind
+    // them: the compiler sinks the prefetch requests past stage 1, to just before its barrier.)
     float wv[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) wv[r] = DIF_W(t, r);
+    for (int r = 0; r < 16; ++r) wv[r] = r < WH ? wh[r] : DIF_W(t, r);
     __builtin_amdgcn_sched_barrier(0);
     const bool more = s + 1 < s1;
     // (addresses from the loop-invariant thread id: computed once, outside the loop)
@@ -845,6 +910,13 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
     } else {
       load_seg(pn, sn, (int)threadIdx.x % T);
     }
+#if ZFFT_DIF_PFPIN
+    // pinned at the segment head: the requests have stages 1 and 2 to arrive before post_sum
+    // reads them.  (Where window loads remain the compiler otherwise sinks them to the end of
+    // stage 1; where none remain it requests here by itself and the pin costs and gains no time,
+    // but it is what keeps the N = 1024 pruned non-overlap forms from spilling: zfft_dif_addr.h.)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
     {
       v2f sum = splat(0.f);
 #pragma unroll
@@ -856,18 +928,40 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
     // stage 1: DFT16 over the thread's own samples, twiddle, store at t + T k
     dft<16>(v);
     apply_powers(v, b1);
+#if ZFFT_DIF_CADDR
+    {  // one base from the opaque t, then constant offsets (immediates of the LDS stores); past
+       // the 16-bit offset field (N = 16384, k >= 8) a second base
+      namespace da = zfft::dif;
+      constexpr int K2 = da::second_base_from(T);
+      v2f *const p0 = img + dif_slot(t);
+      v2f *const p1 = p0 + da::slot_off(T, K2 & 15);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        if (k < K2) p0[da::slot_off(T, k)] = v[k];
+        else p1[da::slot_off(T, k) - da::slot_off(T, K2 & 15)] = v[k];
+      }
+    }
+#else
 #pragma unroll
     for (int k = 0; k < 16; ++k) img[dif_slot(T * k + t)] = v[k];
+#endif
     sync();
     // middle radix-16 stages 2 .. PM
 #pragma unroll
     for (int st = 2; st <= D::PM; ++st) {
       const int S16 = N >> (4 * st), M = S16 * 16;
       const int base = (t / S16) * M + (t & (S16 - 1));
+#if ZFFT_DIF_CADDR
+      // slot(base + S16 m) = slot(base) + slot(S16 m) (zfft_dif_addr.h): constants for every S16
+      v2f *const pm = img + dif_slot(base);
+      auto mid = [&](int m) -> v2f & { return pm[zfft::dif::slot_off(S16, m)]; };
+#else
+      auto mid = [&](int m) -> v2f & { return img[dif_slot(base + S16 * m)]; };
+#endif
 #pragma unroll
-      for (int m = 0; m < 16; ++m) v[m] = img[dif_slot(base + S16 * m)];
+      for (int m = 0; m < 16; ++m) v[m] = mid(m);
       dft<16>(v);
-      if (st == 2) {
+      if (st == 2 && HB2) {
         apply_powers(v, b2);
       } else {
         v2f bs[4];
@@ -876,7 +970,7 @@ void welch_dif_kernel(const v2f *__restrict__ x, int64_t len, const float *__res
         apply_powers(v, bs);
       }
 #pragma unroll
-      for (int k = 0; k < 16; ++k) img[dif_slot(base + S16 * k)] = v[k];
+      for (int k = 0; k < 16; ++k) mid(k) = v[k];
       if (st == D::PM && more) post_sum(pn, (s + 1) & 1, s + 1, t);  // next mean, read after 2 syncs
       sync();
     }
