@@ -862,6 +862,95 @@ int zfft_chan_info(const zfft_plan *plan, double *group_delay, double *rate_rati
 /* No plan, no GPU.  Rule 9: n_chan taps_per_chan float64 values. */
 int zfft_chan_design(int32_t n_chan, int32_t taps_per_chan, double beta, double *h_out);
 
+/* Demodulator bank: AM, FM, SSB and power audio out of complex baseband streams on the device --
+ * what the channeliser and the taps emit.  K streams are detected and low-pass filtered at once by
+ * one shared real audio FIR with an integer decimation; in the power mode the result is the
+ * zero-span trace, power against time on one frequency, with the audio filter as video filter.
+ * Off by default: a plan that never calls zfft_plan_demod allocates and launches nothing.  The
+ * rule (reference: tests/demod_ref.py):
+ *   0. input: complex64 on the device with two strides in complex samples, stream s at step n is
+ *      x[n step_stride + s stream_stride], s < K, 1 <= K <= 1024.  zfft_chan_push_device's output
+ *      is (step_stride, stream_stride) = (K, 1); one tap's output is (1, anything); `count` taps of
+ *      equal decimation written back to back are (1, count).  Nothing is copied or transposed.
+ *      step_stride in [1, 2^31], stream_stride in [1, 2^31] (K = 1: [0, 2^31]).
+ *   1. count: the bank counts steps n = 0, 1, ... from zfft_plan_demod, or from
+ *      zfft_demod_reset(plan, n0), which restarts the count at n0 (0 <= n0 <= 2^62) and zeroes the
+ *      carry; x_s[n] = 0 before the start.  The count and the carry are the bank's own,
+ *      independent of the taps' and the channeliser's.
+ *   2. stream parameters: every stream has a mode and a bfo_word in [-2^31, 2^31), both AM and 0
+ *      after zfft_plan_demod, set between pushes by zfft_demod_mode(plan, s_first, s_count, mode,
+ *      bfo_word) in stream order.  The detected value d_s[n] is a pure function of x = x_s[n],
+ *      p = x_s[n - 1], n and the stream's mode when the push runs, in float32 with every product,
+ *      fused multiply-add and square root rounded once:
+ *        ZFFT_DEMOD_AM     d = sqrt(fma(x.re, x.re, x.im x.im));
+ *        ZFFT_DEMOD_FM     z = x conj(p): z.re = fma(x.re, p.re, x.im p.im), z.im = fma(x.im, p.re,
+ *                          -(x.re p.im)); d = atan2f(z.im, z.re) float32(1 / pi), and d = 0 where
+ *                          z.re = z.im = 0.  +-1 is +-half the stream's rate;
+ *        ZFFT_DEMOD_SSB    d = Re(x r) = fma(x.re, r.re, -(x.im r.im)), r = exp(+2 pi i ((bfo_word
+ *                          n) mod 2^32) / 2^32) in float32 from the integer phase (the taps' rot).
+ *                          A positive word is USB and a negative one LSB, for a stream centred
+ *                          |bfo| off the suppressed carrier;
+ *        ZFFT_DEMOD_POWER  d = fma(x.re, x.re, x.im x.im).
+ *      A mode change therefore applies to the whole carried window and needs no flush.
+ *   3. audio: one real float32 FIR g[0 .. Ta), 1 <= Ta <= 1024, and a decimation Da, 1 <= Da <= 64,
+ *      shared by the bank: a[m, s] = sum_{k < Ta} g[k] d_s[m Da - k] for every m with m Da >= the
+ *      start.  The sum's order is fixed: four partial sums a_j over the k = j (mod 4) in
+ *      ascending k, one fused multiply-add each, then (a_0 + a_1) + (a_2 + a_3).  A push of
+ *      `steps` at count n0 emits the m with n0 <= m Da < n0 + steps: ceil((n0 + steps) / Da) -
+ *      ceil(n0 / Da) of them (zfft_demod_steps, for the next push).  Output is time-major
+ *      float32, out[j K + s] for output j of the push.
+ *   4. carry: the bank carries the last Ta complex inputs of every stream on the device, and the
+ *      outputs are the same bit for bit however the stream is cut into pushes and whichever form
+ *      of the kernel runs (the strides choose it).
+ *   5. the group delay (Ta - 1) / 2 steps is reported (zfft_demod_info), not compensated; the
+ *      output rate is the streams' rate / Da.  zfft_demod_design is zfft_tap_design; g = NULL
+ *      means its 8 Da + 1 taps at cutoff 0.4 / Da, beta 8.  AM's d carries the carrier as a
+ *      constant: a band-pass g that removes it is the caller's choice of g.
+ *   6. |a - a_exact| <= (Ta + 32) 2^-24 sum|g| max|d| + sum|g| eps_mode.  The first term is the
+ *      filter's: each partial sum is at most ceil(Ta / 4) rounded multiply-adds, two adds join
+ *      them, and (Ta / 4 + 2) 2^-24 sum|g d| is below it.  The second carries the detector's error
+ *      |d - d_exact| <= eps_mode through the filter:
+ *        AM     3 2^-24 max|x|: the product and the fma are two roundings of |x|^2, which the
+ *               root halves, and the root's own;
+ *        POWER  3 2^-24 max|x|^2: the same two roundings, second order included;
+ *        SSB    8 2^-24 max|x|: r's components are sincospi within 2 ulp and one fma of the
+ *               small-angle step, 4 2^-24 each, 4 sqrt 2 2^-24 |x| in d; the product and the fma
+ *               of d add 2 2^-24 |x|;
+ *        FM     ZFFT_DEMOD_EPS_FM 2^-24, in units of d (pi radians): the two components of z cost
+ *               about 3 2^-24 rad and the device library's atan2f a few units in its last place.
+ *               That last figure is measured, not derived: twice the worst |d - d_exact| of the
+ *               first run on the device, rounded up (profiles/demod/README.md).  FM has its
+ *               branch at +-1: the bound holds for |arg z| <= 0.9 pi.
+ * zfft_demod_push_device is enqueued on its stream with no sync, ordered after earlier work on
+ * that stream and after the plan's earlier calls on any stream, zfft_demod_mode's included; d_out
+ * must hold zfft_demod_steps x K float32 and not overlap d_x.  Every zfft_demod_* call on a plan
+ * with the bank off returns ZFFT_EINVAL ("demod is off"; zfft_demod_shape after reporting zeros).
+ * With zfft_plan_timing on a push reports its one launch as "demod_push". */
+enum { ZFFT_DEMOD_AM = 0, ZFFT_DEMOD_FM = 1, ZFFT_DEMOD_SSB = 2, ZFFT_DEMOD_POWER = 3 };
+#define ZFFT_DEMOD_EPS_FM 3
+/* n_streams = 0: off, frees everything.  Otherwise n_streams, n_taps, decim as rules 0 and 3,
+ * anything else ZFFT_EINVAL; g: n_taps host floats, or NULL for rule 5's default, with n_taps 0 or
+ * 8 decim + 1.  A call restarts the count at 0 with every stream at AM. */
+int zfft_plan_demod(zfft_plan *plan, int32_t n_streams, int32_t n_taps, int32_t decim, const float *g);
+int zfft_demod_shape(const zfft_plan *plan, int32_t *n_streams, int32_t *n_taps, int32_t *decim);
+/* streams [s_first, s_first + s_count) to `mode` (ZFFT_DEMOD_*) and bfo_word (used by SSB alone) */
+int zfft_demod_mode(zfft_plan *plan, int32_t s_first, int32_t s_count, int32_t mode, int64_t bfo_word);
+/* the outputs a push of `steps` (0 .. 2^31 - 1) now would emit; a pure host function of the count */
+int zfft_demod_steps(const zfft_plan *plan, int64_t steps, int64_t *outputs);
+/* steps (1 .. 2^31 - 1; 0 is ZFFT_OK and does nothing) of the K streams on the device, rule 0 */
+int zfft_demod_push_device(zfft_plan *plan, const void *d_x, int64_t steps, int64_t step_stride,
+                           int64_t stream_stride, void *d_out, void *stream);
+/* host input ((steps - 1) step_stride + (K - 1) stream_stride + 1 complex64) and outputs;
+ * outputs_out (or NULL) as zfft_demod_steps before the push; synchronous */
+int zfft_demod_push(zfft_plan *plan, const void *x, int64_t steps, int64_t step_stride, int64_t stream_stride,
+                    void *out, int64_t *outputs_out);
+int zfft_demod_state(zfft_plan *plan, uint64_t *steps_seen);
+int zfft_demod_reset(zfft_plan *plan, int64_t n0);
+/* group_delay = (Ta - 1) / 2 steps; rate_ratio = 1 / Da outputs per step */
+int zfft_demod_info(const zfft_plan *plan, double *group_delay, double *rate_ratio);
+/* No plan, no GPU.  zfft_tap_design for n_taps in [1, 1024]. */
+int zfft_demod_design(int32_t n_taps, double cutoff, double beta, double *h_out);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

@@ -99,6 +99,8 @@ EXPORTS = [
     "zfft_tap_table",
     "zfft_plan_chan", "zfft_chan_shape", "zfft_chan_select", "zfft_chan_steps", "zfft_chan_push_device",
     "zfft_chan_push", "zfft_chan_state", "zfft_chan_reset", "zfft_chan_info", "zfft_chan_design",
+    "zfft_plan_demod", "zfft_demod_shape", "zfft_demod_mode", "zfft_demod_steps", "zfft_demod_push_device",
+    "zfft_demod_push", "zfft_demod_state", "zfft_demod_reset", "zfft_demod_info", "zfft_demod_design",
 ]
 
 _lib = None
@@ -255,6 +257,16 @@ def load(path: str = ""):
         "zfft_chan_reset": (ctypes.c_int, [P, I64]),
         "zfft_chan_info": (ctypes.c_int, [P, ctypes.POINTER(D), ctypes.POINTER(D)]),
         "zfft_chan_design": (ctypes.c_int, [I32, I32, D, P]),
+        "zfft_plan_demod": (ctypes.c_int, [P, I32, I32, I32, P]),
+        "zfft_demod_shape": (ctypes.c_int, [P] + [ctypes.POINTER(I32)] * 3),
+        "zfft_demod_mode": (ctypes.c_int, [P, I32, I32, I32, I64]),
+        "zfft_demod_steps": (ctypes.c_int, [P, I64, ctypes.POINTER(I64)]),
+        "zfft_demod_push_device": (ctypes.c_int, [P, P, I64, I64, I64, P, P]),
+        "zfft_demod_push": (ctypes.c_int, [P, P, I64, I64, I64, P, P]),
+        "zfft_demod_state": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_uint64)]),
+        "zfft_demod_reset": (ctypes.c_int, [P, I64]),
+        "zfft_demod_info": (ctypes.c_int, [P, ctypes.POINTER(D), ctypes.POINTER(D)]),
+        "zfft_demod_design": (ctypes.c_int, [I32, D, D, P]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "zfft_chan_plan.h"    // the channeliser's forms (ChanForm)
+#include "zfft_demod_plan.h"   // the demodulator bank's forms (DemodForm, DemodCut)
 #include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
 #include "zfft_history_plan.h"  // the row history's quantiser and forms (HistQuant, HistForm)
 #include "zfft_tap_plan.h"     // the channel taps' forms and items (TapForm, TapItems)
@@ -532,6 +533,17 @@ hipError_t launch_tap_push(const void *in, int dtype, int64_t n, int max_len, co
 hipError_t launch_chan_push(const void *in, int dtype, int64_t n, int M, int P, int D, int c_first, int K,
                             const ChanForm &f, const float *h, const float2 *tw, const float2 *carry_old,
                             float2 *carry_new, float2 *out, hipStream_t st);
+// Demodulator bank (zfft.h's rule of zfft_plan_demod; demod_kernels.hip): one push of `steps` steps
+// of K complex64 streams at x[step * step_stride + stream * stream_stride], count n0 at the first,
+// as choose_demod and demod_cut tiled it.  taps holds the Ta audio taps, par K (mode, bfo_word)
+// pairs; carry_old the Ta steps before the push ([row * K + stream]), carry_new those before the
+// next; out[j * K + stream].  x, out and the carries do not overlap.
+hipError_t launch_demod_push(const float2 *x, int64_t steps, int64_t step_stride, int64_t stream_stride, uint64_t n0,
+                             int K, int Ta, int Da, const DemodForm &f, const DemodCut &c, const float *taps,
+                             const uint32_t *par, const float2 *carry_old, float2 *carry_new, float *out,
+                             hipStream_t st);
+// par[s_first .. s_first + s_count) = (mode, word), in stream order.
+hipError_t launch_demod_mode(uint32_t *par, int s_first, int s_count, uint32_t mode, uint32_t word, hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

@@ -387,6 +387,7 @@ int zfft_plan_destroy(zfft_plan *p) {
   if (p->row_pin) (void)hipHostFree(p->row_pin);
   tap_release(p);  // (its page-locked staging)
   chan_release(p);
+  demod_release(p);
   for (hipEvent_t ev : p->events) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : {p->done_ev, p->fork_ev, p->join_ev, p->h2d_ev[0], p->h2d_ev[1], p->comp_ev[0],
                         p->comp_ev[1]})

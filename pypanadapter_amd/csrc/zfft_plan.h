@@ -1,6 +1,6 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
-// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_tap.cpp, zfft_chan.cpp).  Not part of
+// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp).  Not part of
 // the C-ABI.
 #pragma once
 
@@ -16,6 +16,7 @@
 namespace zfft {
 
 struct ChanState;  // zfft_chan.cpp
+struct DemodState;  // zfft_demod.cpp
 
 // A grow-only device buffer, freed with its owner.
 struct DevBuf {
@@ -185,6 +186,8 @@ struct zfft_plan {
   float2 *tp_pin = nullptr;
   // channeliser (zfft_plan_chan; zfft_chan.cpp): null = off (nothing allocated); the state is that file's
   zfft::ChanState *chan = nullptr;
+  // demodulator bank (zfft_plan_demod; zfft_demod.cpp): null = off (nothing allocated); the state is that file's
+  zfft::DemodState *demod = nullptr;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the
@@ -277,6 +280,10 @@ void tap_release(zfft_plan *p);
 // --- zfft_chan.cpp ---
 // Frees the channeliser and switches it off (the caller has waited for the plan's work).
 void chan_release(zfft_plan *p);
+
+// --- zfft_demod.cpp ---
+// Frees the demodulator bank and switches it off (the caller has waited for the plan's work).
+void demod_release(zfft_plan *p);
 
 // --- zfft_welch.cpp ---
 // The Welch rows (or lines) of `frames` decimated frames of Ld samples at x into d_rows, by the

@@ -789,6 +789,94 @@ class ZoomFFT:
         c = (c0 + np.arange(k)) % m
         return np.where(c >= m // 2, c - m, c) * (self.fs / m)
 
+    # ---------------------------------------------------------------- demodulator bank
+    DEMOD_MODES = {"am": 0, "fm": 1, "ssb": 2, "power": 3}
+
+    def set_demod(self, streams: int, taps=None, decim: int = 1) -> None:
+        """Demodulator bank (zfft_plan_demod): AM, FM, SSB or power audio out of `streams` (at
+        most 1024) complex baseband streams on the device -- what `chan_push_device` and
+        `tap_push_device` write -- through one shared real audio FIR `taps` (at most 1024 taps;
+        None designs `demod_design(8 * decim + 1, 0.4 / decim)`) decimating by `decim` (1 .. 64).
+        set_demod(0) turns it off and frees it.  A call restarts the step count with every stream
+        at AM.  The rule is in include/zfft.h, reproducible in numpy (tests/demod_ref.py)."""
+        if int(streams) == 0:
+            check(self.lib.zfft_plan_demod(self._plan, 0, 0, 0, None), "zfft_plan_demod")
+            return
+        if taps is None:
+            check(self.lib.zfft_plan_demod(self._plan, int(streams), 0, int(decim), None), "zfft_plan_demod")
+            return
+        g = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        check(self.lib.zfft_plan_demod(self._plan, int(streams), g.size, int(decim), g.ctypes.data_as(ctypes.c_void_p)),
+              "zfft_plan_demod")
+
+    def demod_shape(self):
+        """(streams, n_taps, decim)."""
+        v = [ctypes.c_int32() for _ in range(3)]
+        check(self.lib.zfft_demod_shape(self._plan, *[ctypes.byref(x) for x in v]), "zfft_demod_shape")
+        return tuple(x.value for x in v)
+
+    def demod_mode(self, mode, bfo_hz: float = 0.0, rate: float | None = None, first: int = 0,
+                   count: int | None = None) -> float:
+        """Streams [first, first + count) (default: all from `first`) to `mode` ("am", "fm", "ssb",
+        "power" or a ZFFT_DEMOD_* value); bfo_hz is SSB's beat frequency at the streams' sample
+        rate `rate` (default: the plan's fs), positive for USB and negative for LSB.  Returns the
+        frequency actually used, a multiple of rate / 2^32.  Applies to the next push, carried
+        window included."""
+        m = self.DEMOD_MODES[mode.lower()] if isinstance(mode, str) else int(mode)
+        rate = self.fs if rate is None else float(rate)
+        word = (int(round(float(bfo_hz) / rate * 2.0 ** 32)) + 2 ** 31) % 2 ** 32 - 2 ** 31
+        if count is None:
+            count = self.demod_shape()[0] - int(first)
+        check(self.lib.zfft_demod_mode(self._plan, int(first), int(count), m, word), "zfft_demod_mode")
+        return word * rate / 2.0 ** 32
+
+    def demod_steps(self, steps: int) -> int:
+        """Outputs of a push of `steps` steps now."""
+        v = ctypes.c_int64()
+        check(self.lib.zfft_demod_steps(self._plan, int(steps), ctypes.byref(v)), "zfft_demod_steps")
+        return v.value
+
+    def demod_push(self, x) -> np.ndarray:
+        """The next steps of the streams from the host: complex64, (steps, streams) or, for one
+        stream, 1-D; returns (outputs, streams) float32.  Synchronous."""
+        k = self.demod_shape()[0]
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        if x.ndim == 1 and k == 1:
+            x = x.reshape(-1, 1)
+        if x.ndim != 2 or x.shape[1] != k:
+            raise ValueError("demod_push takes (steps, streams) complex64, or 1-D for one stream")
+        out = np.empty((self.demod_steps(x.shape[0]), k), dtype=np.float32)
+        check(self.lib.zfft_demod_push(self._plan, x.ctypes.data_as(ctypes.c_void_p), x.shape[0], k, 1,
+                                       out.ctypes.data_as(ctypes.c_void_p), None), "zfft_demod_push")
+        return out
+
+    def demod_push_device(self, d_x_ptr: int, steps: int, step_stride: int, stream_stride: int, d_out_ptr: int,
+                          stream: int = 0) -> None:
+        """`steps` steps on the device, stream s at step n at complex64 index n * step_stride +
+        s * stream_stride ((streams, 1) for chan_push_device's output, (1, count) for taps written
+        back to back); demod_steps(steps) x streams float32 into d_out_ptr; enqueued on `stream`,
+        no sync."""
+        check(self.lib.zfft_demod_push_device(self._plan, ctypes.c_void_p(d_x_ptr), int(steps), int(step_stride),
+                                              int(stream_stride), ctypes.c_void_p(d_out_ptr),
+                                              ctypes.c_void_p(stream or None)), "zfft_demod_push_device")
+
+    def demod_state(self) -> int:
+        """The steps counted so far."""
+        v = ctypes.c_uint64()
+        check(self.lib.zfft_demod_state(self._plan, ctypes.byref(v)), "zfft_demod_state")
+        return v.value
+
+    def demod_reset(self, n0: int = 0) -> None:
+        """Restart the step count at n0 with an all-zero past; the shape and the modes stay."""
+        check(self.lib.zfft_demod_reset(self._plan, int(n0)), "zfft_demod_reset")
+
+    def demod_info(self) -> dict:
+        """group_delay ((n_taps - 1) / 2 steps: reported, not compensated) and rate_ratio (outputs
+        per step, 1 / decim)."""
+        gd, rr = ctypes.c_double(), ctypes.c_double()
+        check(self.lib.zfft_demod_info(self._plan, ctypes.byref(gd), ctypes.byref(rr)), "zfft_demod_info")
+        return {"group_delay": gd.value, "rate_ratio": rr.value}
+
     # ---------------------------------------------------------------- display viewport
     def set_viewport(self, height: int, width: int, col0: int = 0, col1: int | None = None,
                      detector: str = "max", rows_per_line: int = 1) -> None:
@@ -1155,6 +1243,15 @@ def chan_design(n_chan: int, taps_per_channel: int = 8, beta: float = 8.0) -> np
     out = np.empty(int(n_chan) * int(taps_per_channel), dtype=np.float64)
     check(_lib.load().zfft_chan_design(int(n_chan), int(taps_per_channel), float(beta),
                                        out.ctypes.data_as(ctypes.c_void_p)), "zfft_chan_design")
+    return out
+
+
+def demod_design(n_taps: int, cutoff: float, beta: float = 8.0) -> np.ndarray:
+    """The demodulator bank's audio design (zfft_demod_design; no GPU needed): tap_design for at
+    most 1024 taps; the bank's default is demod_design(8 * decim + 1, 0.4 / decim)."""
+    out = np.empty(max(int(n_taps), 0), dtype=np.float64)
+    check(_lib.load().zfft_demod_design(int(n_taps), float(cutoff), float(beta),
+                                        out.ctypes.data_as(ctypes.c_void_p)), "zfft_demod_design")
     return out
 
 

@@ -830,6 +830,80 @@ class Channelizer:
         self._plan.chan_reset(n0)
 
 
+class Demodulator:
+    """Audio out of what a `Channelizer` or a `Tap` pushes, on the device (ZoomFFT.set_demod; the
+    rule is in include/zfft.h): every stream is detected ("am", "fm", "ssb" or "power") and runs
+    through one shared audio low-pass decimating by `audio_decim`, with its state kept from push
+    to push.
+
+        bank = Channelizer(fs, 64)
+        audio = Demodulator.for_channelizer(bank, "fm", audio_decim=4)
+        a = audio.push(bank.push(chunk))                 # (steps, 64) float32 at audio.rate
+        audio.mode("ssb", bfo_hz=1500.0, first=col, count=1)   # one channel to USB
+
+    The bank lives on its source's plan (one demodulator per source), so a caller who keeps the
+    source's output on the device (`chan_push_device`, `tap_push_device`) can hand it to
+    `plan.demod_push_device` with no copy.  "power" is the zero-span trace: power against time on
+    one frequency, the audio filter acting as video filter.  FM's +-1 is +-rate_in / 2.  The group
+    delay is reported, not compensated."""
+
+    def __init__(self, plan, streams: int, rate_in: float, mode="am", audio_decim: int = 1, taps=None,
+                 bfo_hz: float = 0.0):
+        self._plan, self.streams, self.rate_in = plan, int(streams), float(rate_in)
+        plan.set_demod(self.streams, taps=taps, decim=audio_decim)
+        self.mode(mode, bfo_hz)
+
+    @classmethod
+    def for_channelizer(cls, chan: "Channelizer", mode="am", audio_decim: int = 1, taps=None, bfo_hz: float = 0.0):
+        """One stream per kept channel of `chan`, in the order of its columns; `push` takes what
+        `chan.push` returns.  (A later `chan.select` of another count needs a new Demodulator.)"""
+        return cls(chan._plan, chan._plan.chan_shape()[4], chan.rate, mode, audio_decim, taps, bfo_hz)
+
+    @classmethod
+    def for_tap(cls, tap: "Tap", mode="am", audio_decim: int = 1, slot: int | None = None, taps=None,
+                bfo_hz: float = 0.0):
+        """One stream: the open tap in `slot` (default: the only open one); `push` takes that
+        slot's array of `tap.push`."""
+        if slot is None:
+            (slot,) = tap._plan.tap_open_slots()
+        return cls(tap._plan, 1, tap.rate(slot), mode, audio_decim, taps, bfo_hz)
+
+    def close(self):
+        """Turns the bank off on the source's plan, which stays the source's."""
+        if self._plan is not None:
+            if self._plan._plan.value:  # (the source may have closed its plan already)
+                self._plan.set_demod(0)
+            self._plan = None
+
+    def mode(self, mode, bfo_hz: float = 0.0, first: int = 0, count: int | None = None) -> float:
+        """ZoomFFT.demod_mode at the streams' rate: returns the BFO frequency actually used."""
+        return self._plan.demod_mode(mode, bfo_hz, rate=self.rate_in, first=first, count=count)
+
+    @property
+    def rate(self) -> float:
+        """The audio's rate in Hz: the streams' rate / audio_decim."""
+        return self.rate_in * self._plan.demod_info()["rate_ratio"]
+
+    @property
+    def group_delay(self) -> float:
+        """(n_taps - 1) / 2 steps of the streams."""
+        return self._plan.demod_info()["group_delay"]
+
+    def steps(self, n: int) -> int:
+        return self._plan.demod_steps(n)
+
+    def push(self, y) -> np.ndarray:
+        """(outputs, streams) float32 for the next (steps, streams) complex64 of the source."""
+        return self._plan.demod_push(y)
+
+    @property
+    def steps_seen(self) -> int:
+        return self._plan.demod_state()
+
+    def reset(self, n0: int = 0) -> None:
+        self._plan.demod_reset(n0)
+
+
 class Data:
     """pypanadapter_thread.py's `Data` (T:1400-1483) on the pinned double-buffered IQRing
     (SURVEY §8f-1), same calls: the reader thread's `add(chunk)` (T:2191) and the PSD
