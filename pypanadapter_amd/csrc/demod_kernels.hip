@@ -53,7 +53,14 @@ __device__ __forceinline__ float demod_detect(uint32_t mode, uint32_t word, v2f 
     return __fmaf_rn(c.x, r.x, -__fmul_rn(c.y, r.y));
   }
   const float pw = __fmaf_rn(c.x, c.x, __fmul_rn(c.y, c.y));
-  return mode == ZFFT_DEMOD_AM ? __fsqrt_rn(pw) : pw;
+  if (mode != ZFFT_DEMOD_AM) return pw;
+  // sqrtf is the correctly rounded root (denormals included); __fsqrt_rn is the hardware's
+  // approximation, one unit in the last place off in about one value of twenty-five.  Its
+  // fix-up is some fifteen instructions: the empty asm keeps the compiler from computing it for
+  // every mode and selecting, so a wave with no AM stream branches round it
+  float v = pw;
+  asm volatile("" : "+v"(v));
+  return sqrtf(v);
 }
 
 template <int KIND>

@@ -6,7 +6,10 @@ written straight from the formula with an exact integer phase -- never a call in
 x is whatever the plan's in_dtype loader makes of the caller's samples in float32 (`loader`), 0
 before the start of the count.  The error gate is derived, not measured (`gate`): T rounded
 products in a fixed-order float32 sum, the table's rounding, and the rotation's phase, sincos and
-complex multiply bound |y - y_ref| by (T + 32) 2^-24 sum|h| max|x|."""
+complex multiply bound |y - y_ref| by (T + 32) 2^-24 sum|h| max|x|.
+
+Below that, rule 7 in float32 (tap_f32 on tests/f32_exact.py), rounded where the header says the
+kernel rounds, for the comparisons that are equalities (tests/test_gpu_tap_exact.py)."""
 import numpy as np
 
 TWO32 = 1 << 32
@@ -93,3 +96,54 @@ def noise_and_tones(n, seed, fs=1.0, tones=((0.013, 0.5), (-0.21, 0.25))):
     for f, a in tones:
         x += a * np.exp(2j * np.pi * f * t)
     return x.astype(np.complex64)
+
+
+# ---------------------------------------------------------------- the rule in float32, bit for bit
+def quarter_word(D):
+    """A freq_word with (fw D) mod 2^30 == 0, so that rot(m) is always a whole quarter turn, and a
+    fully complex table: 5 2^30 / gcd(D, 2^30), or None where D leaves only the multiples
+    of 2^30 (whose table is real or imaginary)."""
+    p = 1
+    while D % (2 * p) == 0:
+        p *= 2
+    return None if p == 1 else ((5 << 30) // p + (1 << 31)) % TWO32 - (1 << 31)
+
+
+def tap_f32(x, n_first, fw, D, c, ms, block=1 << 15):
+    """Rule 7 in float32 (tests/f32_exact.py), bit for bit: y[m], m in ms, for the stream whose sample
+    n_first + i is the loader's float32 value x[i] (complex64) and every other sample 0, with the
+    table c = zfft_tap_table(fw, h).  Four partial sums a_j over the k = j (mod 4) in ascending k from
+    +0, each step two fmas per component in the header's order (re: fma(c.re, x.re, a.re), then
+    fma(-c.im, x.im, .); im: fma(c.re, x.im, a.im), then fma(c.im, x.re, .)), joined as (a_0 + a_1) +
+    (a_2 + a_3); then the rotation rot(m) = exp(-2 pi i ((fw m D) mod 2^32) / 2^32), restricted to
+    (fw D) mod 2^30 == 0, where it is exactly 1, -i, -1 or i and the product a swap and a sign."""
+    import f32_exact as fx
+    assert (int(fw) * int(D)) % (1 << 30) == 0, (fw, D)
+    x = np.ascontiguousarray(x, dtype=np.complex64)
+    c = np.ascontiguousarray(c, dtype=np.complex64)
+    T = c.size
+    c_re, c_im = np.ascontiguousarray(c.real), np.ascontiguousarray(c.imag)
+    xp = np.concatenate([np.zeros(T - 1, np.complex64), x])
+    x_re, x_im = np.ascontiguousarray(xp.real), np.ascontiguousarray(xp.imag)
+    at = np.array([int(m) * int(D) - int(n_first) + T - 1 for m in ms], dtype=np.int64)
+    assert at.size == 0 or (at.min() >= T - 1 and at.max() < xp.size)
+    out = np.zeros(at.size, np.complex64)
+    for b in range(0, at.size, block):
+        i = at[b:b + block]
+        re = [np.zeros(i.size, np.float32) for _ in range(4)]
+        im = [np.zeros(i.size, np.float32) for _ in range(4)]
+        for k in range(T):
+            j, vr, vi = k & 3, x_re[i - k], x_im[i - k]
+            re[j] = fx.fma(-c_im[k], vi, fx.fma(c_re[k], vr, re[j]))
+            im[j] = fx.fma(c_im[k], vr, fx.fma(c_re[k], vi, im[j]))
+        y_re = fx.add(fx.add(re[0], re[1]), fx.add(re[2], re[3]))
+        y_im = fx.add(fx.add(im[0], im[1]), fx.add(im[2], im[3]))
+        q = np.array([((((int(fw) % TWO32) * ((int(m) * int(D)) % TWO32)) % TWO32) >> 30) for m in ms[b:b + block]])
+        out[b:b + block].real = np.choose(q, [y_re, y_im, -y_re, -y_im])      # rot = 1, -i, -1, i
+        out[b:b + block].imag = np.choose(q, [y_im, -y_re, -y_im, y_re])
+    return out
+
+
+def model_push(x, n0, fw, D, c, n_open=None):
+    """All outputs of one push of x at count n0 (the past all zero), in float32."""
+    return tap_f32(x, n0, fw, D, c, outputs(n0, n0 if n_open is None else n_open, len(x), D))

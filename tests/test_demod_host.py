@@ -233,3 +233,54 @@ def test_new_names_signatures_and_null_plan_errors(zfft_lib):
     for name, v in (("AM", dr.AM), ("FM", dr.FM), ("SSB", dr.SSB), ("POWER", dr.POWER)):
         assert f"ZFFT_DEMOD_{name} = {v}" in rule
     assert f"#define ZFFT_DEMOD_EPS_FM {dr.EPS_FM}\n" in rule and dr.EPS_FM <= 16
+
+
+# ---------------------------------------------------------------- the rule in float32 (demod_ref's model)
+def test_the_float32_model_is_inside_the_float64_gate_on_every_case(zfft_lib):
+    """detect_f32 and fir_f32 (the header's rules 2 and 3, rounded where the header rounds) against
+    the float64 reference under rule 6's gate, on the GPU tests' cases and signals, in every mode the
+    host models: AM, POWER and SSB at the four quarter-turn words."""
+    for i, (K, Ta, Da, layout) in enumerate(dr.CASES):
+        f = demod_form(zfft_lib, K, Ta, Da, *dr.strides(layout, K, 5000))
+        n = dr.case_len(f["span"])
+        x = dr.noise_and_tones(n, K, 7 + i)
+        g = dr.audio_taps(Ta, Da)
+        xmax = np.abs(x).max()
+        for m, words in ((dr.AM, 0), (dr.POWER, 0), (dr.SSB, np.array(dr.QUARTER_WORDS)[np.arange(K) % 4])):
+            a = dr.model_push(x, 0, m, words, g, Da)
+            ref = dr.ref_push(x, 0, m, words, g, Da)
+            assert a.dtype == np.float32 and a.shape == ref.shape == (dr.steps(0, n, Da), K)
+            ratio = np.abs(a.astype(np.float64) - ref).max() / dr.gate(g, m, xmax)
+            assert ratio <= 1.0, (dr.IDS[i], m, ratio)
+            assert np.abs(a.astype(np.float64) - ref).max() > 0 or Ta == 1    # (float32 it is: not the reference again)
+    # FM's z and its zero predicate: the float64 product within two roundings, zero where x or p is
+    x = dr.fm_signal(500, 3, 5)
+    x[[7, 100, 101]] = 0
+    z_re, z_im = dr.fm_z_f32(x)
+    z = x.astype(np.complex128) * np.conj(np.vstack([np.zeros((1, 3)), x[:-1].astype(np.complex128)]))
+    assert np.abs(z_re - z.real).max() <= 3 * dr.U * 1.2 and np.abs(z_im - z.imag).max() <= 3 * dr.U * 1.2
+    assert np.array_equal(dr.fm_zero_f32(x), z == 0) and dr.fm_zero_f32(x).sum() == 3 * 6   # steps 0, 7, 8, 100, 101, 102
+    tiny = np.full((4, 1), 2.0 ** -75 * (1 + 1j), np.complex64)         # x != 0 but both products underflow
+    assert dr.fm_zero_f32(tiny).all() and not (tiny == 0).any()
+
+
+def test_the_float32_model_does_not_depend_on_the_cut():
+    K, Ta, Da, n0 = 4, 9, 3, 2 ** 32 - 50
+    x = dr.noise_and_tones(300, K, 3)
+    g = dr.audio_taps(Ta, Da)
+    modes, words = [dr.AM, dr.SSB, dr.SSB, dr.POWER], [0, 2 ** 30, -2 ** 31, 0]
+    whole = dr.model_push(x, n0, modes, words, g, Da)
+    assert whole.shape == (dr.steps(n0, len(x), Da), K)
+    at, parts = 0, []
+    for c in (1, 1, Da - 1, Ta - 1, Ta, 50, 300 - 50 - 2 * Ta - Da):
+        lo = max(0, at - (Ta - 1))                        # the carry: Ta - 1 detected steps before the cut
+        d = dr.detect_f32(x[lo:at + c], n0 + lo, modes, words)
+        parts.append(dr.fir_f32(d, g, Da, n0 + at, c, first=n0 + lo))
+        at += c
+    assert at == 300 and np.concatenate(parts).tobytes() == whole.tobytes()
+    for s in range(K):                                    # a stream alone is its column
+        assert dr.model_push(x[:, s:s + 1], n0, modes[s], words[s], g, Da).tobytes() == whole[:, s:s + 1].tobytes()
+    # the comparison the exact tests use: NaN equals NaN, +0 equals -0, nothing else is forgiven
+    a = np.float32([0.0, np.nan, 1.0])
+    assert dr.same(a, np.float32([-0.0, np.nan, 1.0])) and not dr.same(a, np.float32([0.0, np.nan, np.nextafter(np.float32(1), 2)]))
+    assert not dr.same(a, a.astype(np.float64)) and "first at (2,)" in dr.first_difference(a, np.float32([0, np.nan, 2]))

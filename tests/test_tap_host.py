@@ -213,3 +213,40 @@ def test_the_reference_does_not_depend_on_the_cut(zfft_lib):
         # the library's counts for the two pushes [n0, n0 + 1700) and the rest: the reference's cut
         assert hook(n0 + 1700, n0, x.size - 1700, D) == late.size
         assert hook(n0, n0, 1700, D) == ms.size - late.size
+
+
+# ---------------------------------------------------------------- the rule in float32 (tap_ref's model)
+def _f32_cases(D, T):
+    """(fw, h) of the exact comparisons: fw = 0 and a quarter-turn word with a fully complex table
+    (or, where D leaves none, 2^30 and -2^31), with solid taps and with the default design."""
+    from pypanadapter_amd.engine import tap_design
+    q = tp.quarter_word(D)
+    words = [0, q] if q is not None else [0, 2 ** 30, -2 ** 31]
+    return [(fw, h) for fw in words for h in (tp.solid_taps(T, 100 + D), tap_design(T, 0.4 / D, 8.0).astype(np.float32))]
+
+
+def test_the_float32_model_is_inside_the_float64_gate_and_does_not_depend_on_the_cut(zfft_lib):
+    """tap_f32 (the header's rule 7, rounded where the header rounds, on zfft_tap_table's c[k])
+    against the float64 reference under the gate on the GPU tests' push; and equal to itself over a
+    window that holds the T - 1 samples before the outputs asked for."""
+    from pypanadapter_amd.engine import tap_table
+    for D, T in tp.DT_TAPS:
+        n = 2 * 512 + 301 + (T if T > 1024 else 0)
+        x = tp.noise_and_tones(n, 7 + D)
+        for fw, h in _f32_cases(D, T):
+            assert (fw * D) % 2 ** 30 == 0 and -2 ** 31 <= fw < 2 ** 31
+            c = tap_table(fw, h)
+            if fw % 2 ** 30:
+                assert T < 3 or (np.abs(c.real[1:]).min() > 0 and np.abs(c.imag[1:3]).min() > 0)   # fully complex
+            n0 = 2 ** 32 - 100 if D == 8 else 0
+            y = tp.model_push(x, n0, fw, D, c)
+            ref = tp.ref_push(x, n0, fw, D, h)
+            assert y.dtype == np.complex64 and y.shape == ref.shape
+            err = np.abs(y.astype(np.complex128) - ref).max()
+            assert err <= tp.gate(h, np.abs(x).max()), (D, T, fw, err)
+            ms = tp.outputs(n0, n0, n, D)
+            late = ms[ms * D >= n0 + 700]
+            a = int(late[0]) * D - n0 - (T - 1)
+            if a >= 0:
+                assert tp.tap_f32(x[a:], n0 + a, fw, D, c, late).tobytes() == y[ms.size - late.size:].tobytes()
+    assert tp.quarter_word(32) == 5 * 2 ** 25 and tp.quarter_word(3) is None and tp.quarter_word(200) == 5 * 2 ** 27
