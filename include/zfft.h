@@ -116,6 +116,11 @@ int zfft_process_device(zfft_plan *plan, const void *d_iq, int64_t n_samples, in
  * zfft_decimated_length(n_samples, zoom) complex64 samples.  Synchronous, host buffers. */
 int zfft_decimate(zfft_plan *plan, const void *iq, int64_t n_samples, void *out_iq,
                   int64_t *out_len);
+/* The same for n_frames frames in one call (frame-major, as zfft_process takes them), on the
+ * schedule that many frames earn: out_iq receives n_frames x zfft_decimated_length complex64,
+ * frame-major; out_len the length per frame. */
+int zfft_decimate_frames(zfft_plan *plan, const void *iq, int64_t n_samples, int32_t n_frames,
+                         void *out_iq, int64_t *out_len);
 int64_t zfft_decimated_length(int64_t n_samples, int32_t zoom);
 
 /* Waterfall ring: H = n_win/4 rows of n_win floats, reference row order on read. */

@@ -67,7 +67,7 @@ class zfft_history_window(ctypes.Structure):
 
 EXPORTS = [
     "zfft_plan_create", "zfft_plan_destroy", "zfft_process", "zfft_process_device",
-    "zfft_decimate", "zfft_decimated_length", "zfft_waterfall_push", "zfft_waterfall_push_device",
+    "zfft_decimate", "zfft_decimate_frames", "zfft_decimated_length", "zfft_waterfall_push", "zfft_waterfall_push_device",
     "zfft_waterfall_read", "zfft_waterfall_reset", "zfft_waterfall_shape", "zfft_window_values",
     "zfft_plan_tune", "zfft_plan_timing", "zfft_plan_timings", "zfft_plan_timing_names",
     "zfft_plan_path", "zfft_plan_welch", "zfft_plan_average", "zfft_plan_set_lo_frames", "zfft_last_error",
@@ -150,6 +150,7 @@ def load(path: str = ""):
         "zfft_process": (ctypes.c_int, [P, P, I64, I32, P]),
         "zfft_process_device": (ctypes.c_int, [P, P, I64, I32, P, P]),
         "zfft_decimate": (ctypes.c_int, [P, P, I64, P, ctypes.POINTER(I64)]),
+        "zfft_decimate_frames": (ctypes.c_int, [P, P, I64, I32, P, ctypes.POINTER(I64)]),
         "zfft_decimated_length": (I64, [I64, I32]),
         "zfft_waterfall_push": (ctypes.c_int, [P, P]),
         "zfft_waterfall_push_device": (ctypes.c_int, [P, P, I32, P]),

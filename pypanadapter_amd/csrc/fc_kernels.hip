@@ -192,6 +192,21 @@ __device__ __forceinline__ v2f load_sample(__amdgpu_buffer_rsrc_t rs, int64_t L,
     return in ? v : splat(0.f);
   }
 }
+// load_sample in 32-bit sample numbers (no FLIP, no cu8; a frame is < 2^31 bytes): one unsigned
+// compare per sample and no 64-bit lane value kept across the block loop for a run's first block
+template <int DT>
+__device__ __forceinline__ v2f load_sample32(__amdgpu_buffer_rsrc_t rs, int L, int n) {
+  static_assert(DT != kInCU8, "raw 0 is not cu8's 0");
+  const uint32_t vo = (uint32_t)n < (uint32_t)L ? (uint32_t)n * ebytes<DT>() : 0x80000000u;
+  if constexpr (DT == kInC64) {
+    return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, 0, 0));
+  } else if constexpr (DT == kInC32H) {
+    const h2 h = __builtin_bit_cast(h2, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0, 0));
+    return v2f{(float)h.x, (float)h.y};
+  } else {
+    return v2f{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0, 0)), 0.f};
+  }
+}
 // the raw pair (n, n + 1), n = s + 2t + 512 j, of a window inside the frame: voffset from
 // pair_vo (per block), soffset the constant 512 eb j (mirrored for FLIP)
 template <int DT, int FLIP>
@@ -199,15 +214,30 @@ __device__ __forceinline__ uint32_t pair_vo(int64_t L, int64_t s, int t) {
   constexpr int eb = ebytes<DT>();
   return (uint32_t)((FLIP ? L - 2 - s - 7680 - 2 * t : s + 2 * t) * eb);
 }
-template <int DT, int FLIP>
-__device__ __forceinline__ typename RawP<DT>::T load_pair_b(__amdgpu_buffer_rsrc_t rs, uint32_t vo, int j) {
-  constexpr int eb = ebytes<DT>();
-  const int so = 512 * eb * (FLIP ? 15 - j : j);
+template <int DT>
+__device__ __forceinline__ typename RawP<DT>::T load_pair_raw(__amdgpu_buffer_rsrc_t rs, uint32_t vo, int so) {
   typedef typename RawP<DT>::T T;
   constexpr int aux = 2;  // non-temporal: the window is streamed once (-1 % per step, r06fc6)
   if constexpr (DT == kInC64) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, aux));
   else if constexpr (DT == kInCU8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, so, aux));
   else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, aux));
+}
+template <int DT, int FLIP>
+__device__ __forceinline__ typename RawP<DT>::T load_pair_b(__amdgpu_buffer_rsrc_t rs, uint32_t vo, int j) {
+  constexpr int eb = ebytes<DT>();
+  return load_pair_raw<DT>(rs, vo, 512 * eb * (FLIP ? 15 - j : j));
+}
+// FC_TAIL_CARRY (fc_prefetch_plan.h; no FLIP, no cu8): request j of the window whose first byte
+// is w and from which the frame has `left` bytes, through a resource of its own -- its first
+// byte, its bytes inside the frame -- with the lane's offset pf_lane_off alone, so the pair
+// comes back as load_sample gives its two samples: 0 where the frame has ended.  All scalar.
+template <int DT>
+__device__ __forceinline__ typename RawP<DT>::T load_pair_r(const char *w, int left, uint32_t vo, int j) {
+  constexpr int eb = ebytes<DT>();
+  static_assert(DT != kInCU8 && eb % 4 == 0, "whole dwords per sample: the range check is per dword");
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+      (void *)(w + pf_req_base(j, eb)), (short)0, pf_req_bytes(left, j, eb), kBufFlags);
+  return load_pair_raw<DT>(rs, vo, 0);
 }
 // Between two inverse stages whose elements stay inside one wave, the exchange is a 4 x 4
 // transpose of a lane's register index a against two bits of its lane number, one bit at a time
@@ -384,13 +414,27 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   };
 
   auto wstart = [&](int b) -> int64_t { return (int64_t)(512 * S) * b - K; };
-  auto inside = [&](int b) { const int64_t s = wstart(b); return s >= 0 && s + kN <= L; };
+  [[maybe_unused]] auto inside = [&](int b) { const int64_t s = wstart(b); return s >= 0 && s + kN <= L; };
   typename RawP<DT>::T pf[S];  // the next window's pairs KEEP .. 15
   v2f ka[KEEP], kb[KEEP];      // this window's pairs S .. 15 = the next window's 0 .. KEEP-1
+  // TAIL: every request of the next window through a resource of its own, range-checked
+  // against the frame's end (fc_prefetch_plan.h), and not through the frame's at a window start
+  // clamped into the frame.  So every block after a run's first is carried, the frame's last,
+  // overhanging window too: before, that block threw the 13 (14) requests away, reloaded the
+  // whole window sample by sample and waited for it in the open -- once per frame, 2.2 % of
+  // the kernel's bytes at cfg2.  The lane's offset is loop-invariant, the rest scalar (6
+  // instructions a request).  FLIP (mirrored offsets, which run past the frame's first byte),
+  // cu8 (its raw 0 is not the value 0) and zoom 2 keep the clamped start and compile to the
+  // instructions of before, as does every instantiation with FC_TAIL_CARRY=0 (compared
+  // function by function on hipcc -S).
+  constexpr bool TAIL = pf_tail(Z, DT, FLIP);
+  static_assert(!TAIL || (Z != 2 && DT != kInCU8 && !FLIP && pf_elem_bytes(DT) == ebytes<DT>()), "range-checked requests");
+  static_assert(pf_window_start(Z, 0) == -K && pf_window_start(Z, 3) == 3 * 512 * S - K, "the plan's window grid");
   bool carried = false;        // ka, kb and pf hold this block's window
-  // the next window's new pairs, issued on every block from a window start clamped into the
-  // frame (values unused when the next window is not inside it): unconditional call sites, so
-  // the wait before their use counts only what was issued after them.
+  // the next window's new pairs, issued on every block (not TAIL: from a window start clamped
+  // into the frame, values unused when the next window is not inside it; TAIL: of no bytes
+  // after a run's last block): unconditional call sites, so the wait before their use counts
+  // only what was issued after them.
   // They are requested in groups at up to five points of the block (fc_prefetch_plan.h) and not
   // in one burst at its head: a wave's 13 requests back to back wait on the memory pipeline's
   // back-pressure wherever they stand (~2,100 cycles of a block when all follow pass C, the
@@ -403,23 +447,37 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
   static_assert(kPfC64 == kInC64 && kPfC32H == kInC32H && kPfCU8 == kInCU8 && kPfF32R == kInF32R, "formats");
   static_assert(pf_step(Z) == S && pf_valid(Z, DT, FLIP), "the plan requests each new pair once");
   constexpr bool PIN = Z != 2 && pf_count(Z, DT, FLIP, kPfHead) != S;
-  uint32_t pvo = 0;
+  uint32_t pvo = TAIL ? (uint32_t)pf_lane_off(t, ebytes<DT>()) : 0;
+  [[maybe_unused]] const char *const xfr = (const char *)in.p + f * in.stride * ebytes<DT>();  // the frame
+  [[maybe_unused]] const char *nw = xfr;  // TAIL: the next window's first byte, the frame's bytes from there
+  [[maybe_unused]] int nleft = 0;
   auto pf_group = [&](auto point) {
     constexpr int g = decltype(point)::value;
     constexpr int first = pf_first(Z, DT, FLIP, g), n = pf_count(Z, DT, FLIP, g);
     if constexpr (n > 0 && !(FC_KO & 1)) {
       if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = first; i < first + n; ++i) pf[i] = load_pair_b<DT, FLIP>(xrs, pvo, KEEP + i);
+      for (int i = first; i < first + n; ++i) {
+        if constexpr (TAIL) pf[i] = load_pair_r<DT>(nw, nleft, pvo, KEEP + i);
+        else pf[i] = load_pair_b<DT, FLIP>(xrs, pvo, KEEP + i);
+      }
       if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
     }
   };
 #define FC_PF_AT(point) pf_group(std::integral_constant<int, point>{})
   auto issue_pf = [&](int b) {
-    carried = b + 1 < b1 && inside(b + 1);
-    int64_t sn = wstart(b + 1);
-    sn = sn < 0 ? 0 : (sn > L - kN ? L - kN : sn);
-    pvo = pair_vo<DT, FLIP>(L, sn, t);
+    if constexpr (TAIL) {
+      const bool more = b + 1 < b1;  // wstart(b + 1) >= 0: b + 1 >= 1
+      carried = more;
+      const int64_t sn = wstart(b + 1);
+      nw = xfr + sn * ebytes<DT>();
+      nleft = pf_left_bytes(L, sn, ebytes<DT>(), more);
+    } else {
+      carried = b + 1 < b1 && inside(b + 1);
+      int64_t sn = wstart(b + 1);
+      sn = sn < 0 ? 0 : (sn > L - kN ? L - kN : sn);
+      pvo = pair_vo<DT, FLIP>(L, sn, t);
+    }
     FC_PF_AT(kPfHead);
   };
   for (int b = b0; b < b1; ++b) {
@@ -447,9 +505,15 @@ __global__ void __launch_bounds__(256, 2) fc_decim_kernel(InDesc in, const v2f *
       } else {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int64_t n = s + 2 * t + 512 * i;
-          xa[i] = load_sample<DT, FLIP>(xrs, L, n);
-          xb[i] = load_sample<DT, FLIP>(xrs, L, n + 1);
+          if constexpr (TAIL) {
+            const int n = (int)s + 2 * t + 512 * i;
+            xa[i] = load_sample32<DT>(xrs, (int)L, n);
+            xb[i] = load_sample32<DT>(xrs, (int)L, n + 1);
+          } else {
+            const int64_t n = s + 2 * t + 512 * i;
+            xa[i] = load_sample<DT, FLIP>(xrs, L, n);
+            xb[i] = load_sample<DT, FLIP>(xrs, L, n + 1);
+          }
         }
         // A run's first and a frame's end blocks only.  Waiting here leaves nothing of this
         // branch pending where it joins the carried one: without it the carried branch waits

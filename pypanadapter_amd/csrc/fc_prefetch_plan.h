@@ -20,6 +20,9 @@
 #ifndef FC_STEP
 #define FC_STEP 13  // zoom 8's step (zfft_internal.h)
 #endif
+#ifndef FC_TAIL_CARRY
+#define FC_TAIL_CARRY 1  // 0 = one resource per frame and a clamped window start: a frame's last window reloads
+#endif
 // Diagnostic overrides of the zoom-8 / zoom-4 plans, five counts: -DFC_PF_PLAN8=4,4,3,0,2
 
 namespace zfft {
@@ -83,6 +86,36 @@ constexpr bool pf_valid(int Z, int DT, int FLIP) {
     if (pf_count(Z, DT, FLIP, g) < 0) return false;
   return pf_total(Z, DT, FLIP) == pf_step(Z);
 }
+
+// Range-checked requests (FC_TAIL_CARRY).  Request j of a window that starts at sample s >= 0 of
+// a frame of L samples is the 512 samples from s + 512 j on, a pair (2t, 2t + 1) of them per lane
+// t.  It goes through a buffer resource of its own: the base is the request's first byte, the
+// size the frame's bytes left from there, at most the request's, and the lane's offset is all
+// the address there is, so the range check returns exactly the frame's samples and 0 past its
+// end, dword by dword (a pair that straddles the end gives one sample and one 0; every element
+// here is whole dwords), whatever the hardware does with a scalar offset.  With that a window
+// that overhangs the frame's end is requested like any other, and only a run's first window,
+// which may start before the frame, loads sample by sample.
+// Which instantiations: those that request in pieces, without FLIP (mirrored offsets run down
+// and past the frame's first byte).  Not cu8 (raw 0 is not the value 0, and half a dword).
+constexpr bool pf_tail(int Z, int DT, int FLIP) { return FC_TAIL_CARRY && pf_spread(Z, DT) && !FLIP; }
+constexpr int pf_elem_bytes(int DT) { return DT == kPfC64 ? 8 : DT == kPfCU8 ? 2 : 4; }
+// first sample of block b's window: the blocks advance 512 S samples, the window reaches
+// K = (8192 - 512 S) / 2 before the block's first (fc_kernels.hip asserts its own against this)
+constexpr long long pf_window_start(int Z, int b) { return 512LL * pf_step(Z) * b - (8192 - 512 * pf_step(Z)) / 2; }
+// bytes of the frame from the window start on (0 <= s <= L, and a frame FC takes has < 2^31
+// bytes: 32-bit scalar arithmetic throughout); 0 when no block follows (more = 0), so that a
+// run's last block requests nothing of a window nobody takes
+constexpr int pf_left_bytes(long long L, long long s, int eb, bool more) { return more ? (int)((L - s) * eb) : 0; }
+// the request's first byte from the window's first
+constexpr int pf_req_base(int j, int eb) { return 512 * eb * j; }
+// the size of its resource
+constexpr int pf_req_bytes(int left, int j, int eb) {
+  const int r = left - pf_req_base(j, eb);
+  return r < 0 ? 0 : r > 512 * eb ? 512 * eb : r;
+}
+// the lane's offset into it
+constexpr int pf_lane_off(int t, int eb) { return 2 * t * eb; }
 
 }  // namespace fc
 }  // namespace zfft

@@ -616,13 +616,18 @@ int zfft_process(zfft_plan *p, const void *iq, int64_t L, int32_t frames, float 
 }
 
 int zfft_decimate(zfft_plan *p, const void *iq, int64_t L, void *out_iq, int64_t *out_len) {
+  return zfft_decimate_frames(p, iq, L, 1, out_iq, out_len);
+}
+
+int zfft_decimate_frames(zfft_plan *p, const void *iq, int64_t L, int32_t frames, void *out_iq,
+                         int64_t *out_len) {
   int rc = enter(p);
   if (rc) return rc;
   if (!iq || !out_iq) return fail(ZFFT_EINVAL, "null host pointer");
   std::vector<int64_t> n;
-  rc = check_lengths(p, L, 1, n);
+  rc = check_lengths(p, L, frames, n);
   if (rc) return rc;
-  const size_t in_bytes = (size_t)L * in_elem_bytes(p->cfg.in_dtype);
+  const size_t in_bytes = (size_t)frames * L * in_elem_bytes(p->cfg.in_dtype);
   rc = ensure_lo(p, L);  // (a table upload waits for the plan's earlier work)
   if (rc) return rc;
   hipError_t e = p->in.ensure(in_bytes);
@@ -635,18 +640,18 @@ int zfft_decimate(zfft_plan *p, const void *iq, int64_t L, void *out_iq, int64_t
   mark(p, p->stream, "start");
   const float2 *x;
   if (p->K == 0) {  // zoomfft(x, 1) still mixes (S:2093-2094)
-    e = p->dec.ensure((size_t)L * sizeof(float2));
+    e = p->dec.ensure((size_t)frames * L * sizeof(float2));
     if (e != hipSuccess) return fail(ZFFT_ENOMEM, "allocation failed");
-    e = launch_ingest(input_of(p, p->in.p, L), p->lo.as<float2>(), p->dec.as<float2>(), 1,
+    e = launch_ingest(input_of(p, p->in.p, L), p->lo.as<float2>(), p->dec.as<float2>(), frames,
                       p->stream);
     if (e != hipSuccess) return hip_fail(e, "mix launch");
     x = p->dec.as<float2>();
   } else {
-    rc = run_decimator(p, input_of(p, p->in.p, L), L, 1, n, &x, p->stream);
+    rc = run_decimator(p, input_of(p, p->in.p, L), L, frames, n, &x, p->stream);
     if (rc) return rc;
   }
   const int64_t m = n[p->K];
-  e = hipMemcpyAsync(out_iq, x, (size_t)m * sizeof(float2), hipMemcpyDeviceToHost, p->stream);
+  e = hipMemcpyAsync(out_iq, x, (size_t)frames * m * sizeof(float2), hipMemcpyDeviceToHost, p->stream);
   if (e != hipSuccess) return hip_fail(e, "D2H copy");
   rc = done_on(p, p->stream);
   if (rc) return rc;
