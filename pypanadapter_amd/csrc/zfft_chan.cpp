@@ -1,17 +1,16 @@
 // zfft_chan.cpp -- the channeliser of libzfft.so: a polyphase-FFT bank of M uniform channels on
 // the plan's input samples (C-ABI and rule: zfft.h; kernel: chan_kernels.hip; form chooser, step
-// counts and the transform's layout: zfft_chan_plan.h).  The model is
-// zfft_tap.cpp's: nothing runs inside zfft_process*, the sample count is the host's, and the
-// state on the device is the prototype, the twiddles and two alternating carries.  Its count and
-// carry are its own: the taps neither see nor move them.
-#include <hip/hip_runtime.h>
-
+// counts and the transform's layout: zfft_chan_plan.h).  Nothing runs
+// inside zfft_process*, the sample count is the host's, and the state on the device is the
+// prototype, the twiddles and two alternating carries.  Count, carries and the host push's staging
+// go through the producers' shared path (zfft_stream.h) and are its own: the taps neither see nor
+// move them.
 #include <algorithm>
 #include <vector>
 
 #include "zfft.h"
 #include "zfft_chan_plan.h"
-#include "zfft_plan.h"
+#include "zfft_stream.h"
 
 using namespace zfft;
 
@@ -20,9 +19,8 @@ namespace zfft {
 struct ChanState {
   int M = 0, P = 0, D = 0;
   int c_first = 0, c_count = 0;
-  int par = 0;     // a push reads the carry of this parity and writes the other
-  uint64_t n = 0;  // samples given (host side: pushes are in call order)
-  DevBuf h, tw, carry, stage;  // M P floats; M float2; two carries of M P - 1 samples; zfft_chan_push's staging
+  DevBuf h, tw;    // M P floats; M float2
+  StreamState s;   // samples given; two carries of M P - 1 samples; zfft_chan_push's staging
 };
 
 void chan_release(zfft_plan *p) {
@@ -34,27 +32,26 @@ void chan_release(zfft_plan *p) {
 
 namespace {
 
+constexpr StreamNames kNames{"chan", "n_samples", "sample"};
+
 int need_on(const zfft_plan *p) { return p->chan ? ZFFT_OK : fail(ZFFT_EINVAL, "channels are off (zfft_plan_chan)"); }
 
-size_t carry_len(const ChanState *c) { return (size_t)(c->M * c->P - 1); }
-float2 *carry(const ChanState *c, int par) { return c->carry.as<float2>() + (size_t)par * carry_len(c); }
-
-int check_push(const ChanState *c, int64_t n) {
-  if (n < 1 || n > kChanMaxPush) return fail(ZFFT_EINVAL, "chan push: n_samples in [0, 2^31 - 1]");
-  if (c->n + (uint64_t)n > kChanMaxCount) return fail(ZFFT_EINVAL, "chan push: the sample count would pass 2^62");
-  return ZFFT_OK;
-}
-
-// The count back to n0 and the carry to zeros, in stream order on the plan's stream.
-int restart(zfft_plan *p, uint64_t n0) {
+// A checked push of n_samples >= 1 from device memory, enqueued on the caller's stream.
+int push_on(zfft_plan *p, const void *d_iq, int64_t n_samples, void *d_out, void *hip_stream) {
   ChanState *c = p->chan;
-  int rc = use_stream(p, p->stream);
+  if (!d_iq) return fail(ZFFT_EINVAL, "chan push: null input");
+  const ChanForm f = choose_chan(c->s.n, n_samples, c->M, c->P, c->D, c->c_count);
+  if (!f.ok()) return fail(ZFFT_EINTERNAL, "chan push: no form for this call");
+  if (f.steps > 0 && !d_out) return fail(ZFFT_EINVAL, "chan push: null output");
+  hipStream_t st;
+  int rc = begin_call(p, hip_stream, &st);
   if (rc) return rc;
-  hipError_t e = hipMemsetAsync(c->carry.p, 0, 2 * carry_len(c) * sizeof(float2), p->stream);
-  if (e != hipSuccess) return hip_fail(e, "chan reset");
-  c->n = n0;
-  c->par = 0;
-  return done_on(p, p->stream);
+  hipError_t e = launch_chan_push(d_iq, p->cfg.in_dtype, n_samples, c->M, c->P, c->D, c->c_first, c->c_count, f,
+                                  c->h.as<float>(), c->tw.as<float2>(), c->s.carry_in(), c->s.carry_out(),
+                                  (float2 *)d_out, st);
+  if (e != hipSuccess) return hip_fail(e, "chan_push");
+  mark(p, st, "chan_push");
+  return stream_commit(p, c->s, n_samples, st);
 }
 
 }  // namespace
@@ -94,7 +91,7 @@ int zfft_plan_chan(zfft_plan *p, int32_t n_chan, int32_t taps_per_chan, int32_t 
   c->c_first = 0, c->c_count = M;
   hipError_t e = c->h.ensure((size_t)T * sizeof(float));
   if (e == hipSuccess) e = c->tw.ensure((size_t)M * sizeof(float2));
-  if (e == hipSuccess) e = c->carry.ensure(2 * carry_len(c) * sizeof(float2));
+  if (e == hipSuccess) e = stream_alloc(c->s, (size_t)(T - 1));
   if (e != hipSuccess) {
     (void)hipGetLastError();
     chan_release(p);
@@ -107,7 +104,7 @@ int zfft_plan_chan(zfft_plan *p, int32_t n_chan, int32_t taps_per_chan, int32_t 
     chan_release(p);
     return hip_fail(e, "chan table upload");
   }
-  rc = restart(p, 0);
+  rc = stream_restart(p, c->s, kNames, 0);
   if (rc) chan_release(p);
   return rc;
 }
@@ -125,8 +122,7 @@ int zfft_chan_shape(const zfft_plan *p, int32_t *n_chan, int32_t *taps_per_chan,
 
 int zfft_chan_select(zfft_plan *p, int32_t c_first, int32_t c_count) {
   int rc = enter(p);
-  if (rc) return rc;
-  rc = need_on(p);
+  if (!rc) rc = need_on(p);
   if (rc) return rc;
   ChanState *c = p->chan;
   if (c_first < 0 || c_first >= c->M || c_count < 1 || c_count > c->M)
@@ -140,42 +136,21 @@ int zfft_chan_steps(const zfft_plan *p, int64_t n_samples, int64_t *steps) {
   int rc = need_on(p);
   if (rc) return rc;
   if (n_samples < 0 || n_samples > kChanMaxPush) return fail(ZFFT_EINVAL, "chan_steps: n_samples in [0, 2^31 - 1]");
-  *steps = chan_steps(p->chan->n, n_samples, p->chan->D);
+  *steps = chan_steps(p->chan->s.n, n_samples, p->chan->D);
   return ZFFT_OK;
 }
 
 int zfft_chan_push_device(zfft_plan *p, const void *d_iq, int64_t n_samples, void *d_out, void *hip_stream) {
   int rc = enter(p);
-  if (rc) return rc;
-  rc = need_on(p);
-  if (rc) return rc;
-  if (n_samples == 0) return ZFFT_OK;
-  ChanState *c = p->chan;
-  rc = check_push(c, n_samples);
-  if (rc) return rc;
-  if (!d_iq) return fail(ZFFT_EINVAL, "chan push: null input");
-  const ChanForm f = choose_chan(c->n, n_samples, c->M, c->P, c->D, c->c_count);
-  if (!f.ok()) return fail(ZFFT_EINTERNAL, "chan push: no form for this call");
-  if (f.steps > 0 && !d_out) return fail(ZFFT_EINVAL, "chan push: null output");
-  hipStream_t st = pick_stream(p, hip_stream);
-  rc = use_stream(p, st);
-  if (rc) return rc;
-  p->n_marks = 0;
-  mark(p, st, "start");
-  hipError_t e = launch_chan_push(d_iq, p->cfg.in_dtype, n_samples, c->M, c->P, c->D, c->c_first, c->c_count, f,
-                                  c->h.as<float>(), c->tw.as<float2>(), carry(c, c->par), carry(c, c->par ^ 1),
-                                  (float2 *)d_out, st);
-  if (e != hipSuccess) return hip_fail(e, "chan_push");
-  mark(p, st, "chan_push");
-  c->n += (uint64_t)n_samples;
-  c->par ^= 1;
-  return done_on(p, st);
+  if (!rc) rc = need_on(p);
+  if (rc || n_samples == 0) return rc;
+  rc = stream_check_push(p->chan->s, kNames, n_samples);
+  return rc ? rc : push_on(p, d_iq, n_samples, d_out, hip_stream);
 }
 
 int zfft_chan_push(zfft_plan *p, const void *iq, int64_t n_samples, void *out, int64_t *steps_out) {
   int rc = enter(p);
-  if (rc) return rc;
-  rc = need_on(p);
+  if (!rc) rc = need_on(p);
   if (rc) return rc;
   int64_t steps = 0;
   rc = zfft_chan_steps(p, n_samples, &steps);
@@ -183,39 +158,24 @@ int zfft_chan_push(zfft_plan *p, const void *iq, int64_t n_samples, void *out, i
   if (steps_out) *steps_out = steps;
   if (n_samples == 0) return ZFFT_OK;
   ChanState *c = p->chan;
-  rc = check_push(c, n_samples);
+  rc = stream_check_push(c->s, kNames, n_samples);
   if (rc) return rc;
-  if (!iq || (steps > 0 && !out)) return fail(ZFFT_EINVAL, "chan push: null host pointer");
-  const size_t in_bytes = ((size_t)n_samples * in_elem_bytes(p->cfg.in_dtype) + 15) & ~(size_t)15;
-  const size_t out_bytes = (size_t)steps * (size_t)c->c_count * sizeof(float2);
-  rc = grow(p, c->stage, in_bytes + out_bytes, "chan staging");
-  if (!rc) rc = use_stream(p, p->stream);  // the staging may still be read by the previous call
-  if (rc) return rc;
-  char *d = c->stage.as<char>();
-  hipError_t e = hipMemcpyAsync(d, iq, (size_t)n_samples * in_elem_bytes(p->cfg.in_dtype), hipMemcpyHostToDevice,
-                                p->stream);
-  if (e != hipSuccess) return hip_fail(e, "H2D samples");
-  rc = zfft_chan_push_device(p, d, n_samples, d + in_bytes, p->stream);
-  if (rc) return rc;
-  e = out_bytes ? hipMemcpyAsync(out, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, p->stream) : hipSuccess;
-  return sync_read(p, e, "chan push");
+  return stream_host_push(p, c->s, kNames, iq, (size_t)n_samples * in_elem_bytes(p->cfg.in_dtype), out,
+                          (size_t)steps * (size_t)c->c_count * sizeof(float2),
+                          [=](const void *d_in, void *d_out) { return push_on(p, d_in, n_samples, d_out, p->stream); });
 }
 
 int zfft_chan_state(zfft_plan *p, uint64_t *samples_seen) {
   if (!p || !samples_seen) return fail(ZFFT_EINVAL, "null argument");
   int rc = need_on(p);
-  if (rc) return rc;
-  *samples_seen = p->chan->n;
-  return ZFFT_OK;
+  if (!rc) *samples_seen = p->chan->s.n;
+  return rc;
 }
 
 int zfft_chan_reset(zfft_plan *p, int64_t n0) {
   int rc = enter(p);
-  if (rc) return rc;
-  rc = need_on(p);
-  if (rc) return rc;
-  if (n0 < 0 || (uint64_t)n0 > kChanMaxCount) return fail(ZFFT_EINVAL, "chan_reset: n0 in [0, 2^62]");
-  return restart(p, (uint64_t)n0);
+  if (!rc) rc = need_on(p);
+  return rc ? rc : stream_reset(p, p->chan->s, kNames, n0);
 }
 
 int zfft_chan_info(const zfft_plan *p, double *group_delay, double *rate_ratio) {

@@ -14,8 +14,6 @@ void set_error(const std::string &msg);  // zfft_plan.cpp
 
 namespace {
 
-uint64_t ceil_div(uint64_t a, uint64_t d) { return a / d + (a % d != 0); }
-
 int log2i(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
@@ -27,11 +25,6 @@ int log2i(int v) {
 bool chan_shape_ok(int M, int P, int D) {
   return M >= kChanMinM && M <= kChanMaxM && (M & (M - 1)) == 0 && P >= 1 && P <= kChanMaxLen / M &&
          (D == M || D == M / 2);
-}
-
-int64_t chan_steps(uint64_t n0, int64_t n, int32_t D) {
-  if (n < 0 || D < 1 || n0 > kChanMaxCount || n > kChanMaxPush) return 0;
-  return (int64_t)(ceil_div(n0 + (uint64_t)n, (uint64_t)D) - ceil_div(n0, (uint64_t)D));
 }
 
 ChanForm choose_chan(uint64_t n0, int64_t n, int M, int P, int D, int K) {
@@ -58,8 +51,8 @@ ChanForm choose_chan(uint64_t n0, int64_t n, int M, int P, int D, int K) {
   f.lds_bytes = lds_of(points);
   f.nspans = spans_of(points);
   f.grid = (int)std::min<int64_t>(f.nspans, kChanGridMax);
-  const uint64_t m0 = ceil_div(n0, (uint64_t)D);
-  f.r0 = (int)(m0 * (uint64_t)D - n0);
+  f.r0 = (int)stream_first(n0, D);
+  const uint64_t m0 = (n0 + (uint64_t)f.r0) / (uint64_t)D;  // the first step's m
   f.odd0 = D != M ? (int)(m0 & 1) : 0;
   f.steps = chan_steps(n0, n, D);
   f.span = f.steps_per_span * D;

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "zfft.h"
+#include "zfft_stream_plan.h"
 
 namespace zfft {
 
@@ -23,8 +24,8 @@ constexpr int kChanGridMax = 1024;              // workgroups of a launch: they 
 constexpr int kChanLdsMax = 64 * 1024;          // bytes of LDS a launch may ask for without an attribute
 constexpr int kChanRegTaps = 8;                 // P up to here: a lane keeps its coefficients in registers
 constexpr int kChanMaxPasses = 5;               // log4(1024)
-constexpr int64_t kChanMaxPush = INT32_MAX;           // samples of a push
-constexpr uint64_t kChanMaxCount = (uint64_t)1 << 62; // the plan's sample count (zfft_chan_reset)
+constexpr int64_t kChanMaxPush = kStreamMaxPush;      // samples of a push
+constexpr uint64_t kChanMaxCount = kStreamMaxCount;   // the plan's sample count (zfft_chan_reset)
 
 enum ChanKind {
   kChanRegs = 0,  // P <= kChanRegTaps: the R1 P coefficients of a lane's branches live in registers
@@ -55,8 +56,8 @@ struct ChanForm {
 bool chan_shape_ok(int M, int P, int D);
 
 // ceil((n0 + n) / D) - ceil(n0 / D): the steps of a push of n samples at count n0 (the rule's
-// item 4; the count starts at the reset value, so n_start <= n0).  0 outside n >= 0, D >= 1.
-int64_t chan_steps(uint64_t n0, int64_t n, int32_t D);
+// item 4; the count starts at the reset value, so n_start <= n0: stream_count).  0 outside n >= 0, D >= 1.
+inline int64_t chan_steps(uint64_t n0, int64_t n, int32_t D) { return stream_count(n0, n0, n, D); }
 
 // The form of a push of n samples at count n0 with K kept channels.  !ok() outside 1 <= n <= 2^31 - 1,
 // n0 <= 2^62, a valid shape, 1 <= K <= M.

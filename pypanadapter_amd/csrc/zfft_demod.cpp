@@ -1,17 +1,16 @@
 // zfft_demod.cpp -- the demodulator bank of libzfft.so: AM, FM, SSB and power audio out of K
 // complex baseband streams on the device (C-ABI and rule: zfft.h; kernel: demod_kernels.hip; form
-// chooser and output counts: zfft_demod_plan.h).  The model is zfft_chan.cpp's:
-// nothing runs inside zfft_process*, the step count is the host's, and the state on the device is
-// the audio taps, a (mode, bfo_word) pair per stream and two alternating carries.  A mode change
-// is one small launch on the plan's stream, so it needs no host memory that outlives the call.
-#include <hip/hip_runtime.h>
-
+// chooser and output counts: zfft_demod_plan.h).  Nothing runs inside
+// zfft_process*, the step count is the host's, and the state on the device is the audio taps, a
+// (mode, bfo_word) pair per stream and two alternating carries.  Count, carries and the host push's
+// staging go through the producers' shared path (zfft_stream.h).  A mode change is one small
+// launch on the plan's stream, so it needs no host memory that outlives the call.
 #include <algorithm>
 #include <vector>
 
 #include "zfft.h"
 #include "zfft_demod_plan.h"
-#include "zfft_plan.h"
+#include "zfft_stream.h"
 
 using namespace zfft;
 
@@ -19,9 +18,8 @@ namespace zfft {
 
 struct DemodState {
   int K = 0, Ta = 0, Da = 0;
-  int par = 0;     // a push reads the carry of this parity and writes the other
-  uint64_t n = 0;  // steps given (host side: pushes are in call order)
-  DevBuf g, modes, carry, stage;  // Ta floats; K (mode, word) pairs; two carries of Ta K samples; zfft_demod_push's staging
+  DevBuf g, modes;  // Ta floats; K (mode, word) pairs
+  StreamState s;    // steps given; two carries of Ta K samples; zfft_demod_push's staging
 };
 
 void demod_release(zfft_plan *p) {
@@ -33,29 +31,37 @@ void demod_release(zfft_plan *p) {
 
 namespace {
 
+constexpr StreamNames kNames{"demod", "steps", "step"};
+
 int need_on(const zfft_plan *p) { return p->demod ? ZFFT_OK : fail(ZFFT_EINVAL, "demod is off (zfft_plan_demod)"); }
 
-size_t carry_len(const DemodState *d) { return (size_t)d->Ta * (size_t)d->K; }
-float2 *carry(const DemodState *d, int par) { return d->carry.as<float2>() + (size_t)par * carry_len(d); }
-
 int check_push(const DemodState *d, int64_t steps, int64_t step_stride, int64_t stream_stride) {
-  if (steps < 1 || steps > kDemodMaxPush) return fail(ZFFT_EINVAL, "demod push: steps in [0, 2^31 - 1]");
-  if (d->n + (uint64_t)steps > kDemodMaxCount) return fail(ZFFT_EINVAL, "demod push: the step count would pass 2^62");
+  int rc = stream_check_push(d->s, kNames, steps);
+  if (rc) return rc;
   if (!demod_strides_ok(d->K, step_stride, stream_stride))
     return fail(ZFFT_EINVAL, "demod push: step_stride in [1, 2^31], stream_stride in [1, 2^31] (one stream: [0, 2^31])");
   return ZFFT_OK;
 }
 
-// The count back to n0 and the carry to zeros, in stream order on the plan's stream.
-int restart(zfft_plan *p, uint64_t n0) {
+// A checked push of steps >= 1 from device memory, enqueued on the caller's stream.
+int push_on(zfft_plan *p, const void *d_x, int64_t steps, int64_t step_stride, int64_t stream_stride, void *d_out,
+            void *hip_stream) {
   DemodState *d = p->demod;
-  int rc = use_stream(p, p->stream);
+  if (!d_x) return fail(ZFFT_EINVAL, "demod push: null input");
+  if (((uintptr_t)d_x & 7) || ((uintptr_t)d_out & 3)) return fail(ZFFT_EINVAL, "demod push: misaligned pointer");
+  const DemodForm f = choose_demod(d->K, d->Ta, d->Da, step_stride, stream_stride);
+  const DemodCut c = demod_cut(f, d->s.n, steps, d->Da);
+  if (!f.ok() || !c.ok()) return fail(ZFFT_EINTERNAL, "demod push: no form for this call");
+  if (c.outs > 0 && !d_out) return fail(ZFFT_EINVAL, "demod push: null output");
+  hipStream_t st;
+  int rc = begin_call(p, hip_stream, &st);
   if (rc) return rc;
-  hipError_t e = hipMemsetAsync(d->carry.p, 0, 2 * carry_len(d) * sizeof(float2), p->stream);
-  if (e != hipSuccess) return hip_fail(e, "demod reset");
-  d->n = n0;
-  d->par = 0;
-  return done_on(p, p->stream);
+  hipError_t e = launch_demod_push((const float2 *)d_x, steps, step_stride, stream_stride, d->s.n, d->K, d->Ta, d->Da, f, c,
+                                   d->g.as<float>(), d->modes.as<uint32_t>(), d->s.carry_in(), d->s.carry_out(),
+                                   (float *)d_out, st);
+  if (e != hipSuccess) return hip_fail(e, "demod_push");
+  mark(p, st, "demod_push");
+  return stream_commit(p, d->s, steps, st);
 }
 
 }  // namespace
@@ -94,7 +100,7 @@ int zfft_plan_demod(zfft_plan *p, int32_t n_streams, int32_t n_taps, int32_t dec
   d->K = K, d->Ta = Ta, d->Da = decim;
   hipError_t e = d->g.ensure((size_t)Ta * sizeof(float));
   if (e == hipSuccess) e = d->modes.ensure((size_t)K * 2 * sizeof(uint32_t));
-  if (e == hipSuccess) e = d->carry.ensure(2 * carry_len(d) * sizeof(float2));
+  if (e == hipSuccess) e = stream_alloc(d->s, (size_t)Ta * (size_t)K);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     demod_release(p);
@@ -108,7 +114,7 @@ int zfft_plan_demod(zfft_plan *p, int32_t n_streams, int32_t n_taps, int32_t dec
     return hip_fail(e, "demod table upload");
   }
   static_assert(ZFFT_DEMOD_AM == 0, "a zeroed pair is AM");
-  rc = restart(p, 0);
+  rc = stream_restart(p, d->s, kNames, 0);
   if (rc) demod_release(p);
   return rc;
 }
@@ -124,8 +130,7 @@ int zfft_demod_shape(const zfft_plan *p, int32_t *n_streams, int32_t *n_taps, in
 
 int zfft_demod_mode(zfft_plan *p, int32_t s_first, int32_t s_count, int32_t mode, int64_t bfo_word) {
   int rc = enter(p);
-  if (rc) return rc;
-  rc = need_on(p);
+  if (!rc) rc = need_on(p);
   if (rc) return rc;
   DemodState *d = p->demod;
   if (s_first < 0 || s_count < 1 || s_first >= d->K || s_count > d->K - s_first || mode < ZFFT_DEMOD_AM ||
@@ -146,46 +151,23 @@ int zfft_demod_steps(const zfft_plan *p, int64_t steps, int64_t *outputs) {
   int rc = need_on(p);
   if (rc) return rc;
   if (steps < 0 || steps > kDemodMaxPush) return fail(ZFFT_EINVAL, "demod_steps: steps in [0, 2^31 - 1]");
-  *outputs = demod_steps(p->demod->n, steps, p->demod->Da);
+  *outputs = demod_steps(p->demod->s.n, steps, p->demod->Da);
   return ZFFT_OK;
 }
 
 int zfft_demod_push_device(zfft_plan *p, const void *d_x, int64_t steps, int64_t step_stride, int64_t stream_stride,
                            void *d_out, void *hip_stream) {
   int rc = enter(p);
-  if (rc) return rc;
-  rc = need_on(p);
-  if (rc) return rc;
-  if (steps == 0) return ZFFT_OK;
-  DemodState *d = p->demod;
-  rc = check_push(d, steps, step_stride, stream_stride);
-  if (rc) return rc;
-  if (!d_x) return fail(ZFFT_EINVAL, "demod push: null input");
-  if (((uintptr_t)d_x & 7) || ((uintptr_t)d_out & 3)) return fail(ZFFT_EINVAL, "demod push: misaligned pointer");
-  const DemodForm f = choose_demod(d->K, d->Ta, d->Da, step_stride, stream_stride);
-  const DemodCut c = demod_cut(f, d->n, steps, d->Da);
-  if (!f.ok() || !c.ok()) return fail(ZFFT_EINTERNAL, "demod push: no form for this call");
-  if (c.outs > 0 && !d_out) return fail(ZFFT_EINVAL, "demod push: null output");
-  hipStream_t st = pick_stream(p, hip_stream);
-  rc = use_stream(p, st);
-  if (rc) return rc;
-  p->n_marks = 0;
-  mark(p, st, "start");
-  hipError_t e = launch_demod_push((const float2 *)d_x, steps, step_stride, stream_stride, d->n, d->K, d->Ta, d->Da, f, c,
-                                   d->g.as<float>(), d->modes.as<uint32_t>(), carry(d, d->par), carry(d, d->par ^ 1),
-                                   (float *)d_out, st);
-  if (e != hipSuccess) return hip_fail(e, "demod_push");
-  mark(p, st, "demod_push");
-  d->n += (uint64_t)steps;
-  d->par ^= 1;
-  return done_on(p, st);
+  if (!rc) rc = need_on(p);
+  if (rc || steps == 0) return rc;
+  rc = check_push(p->demod, steps, step_stride, stream_stride);
+  return rc ? rc : push_on(p, d_x, steps, step_stride, stream_stride, d_out, hip_stream);
 }
 
 int zfft_demod_push(zfft_plan *p, const void *x, int64_t steps, int64_t step_stride, int64_t stream_stride, void *out,
                     int64_t *outputs_out) {
   int rc = enter(p);
-  if (rc) return rc;
-  rc = need_on(p);
+  if (!rc) rc = need_on(p);
   if (rc) return rc;
   int64_t outs = 0;
   rc = zfft_demod_steps(p, steps, &outs);
@@ -195,37 +177,24 @@ int zfft_demod_push(zfft_plan *p, const void *x, int64_t steps, int64_t step_str
   DemodState *d = p->demod;
   rc = check_push(d, steps, step_stride, stream_stride);
   if (rc) return rc;
-  if (!x || (outs > 0 && !out)) return fail(ZFFT_EINVAL, "demod push: null host pointer");
   const size_t count = (size_t)(steps - 1) * (size_t)step_stride + (size_t)(d->K - 1) * (size_t)stream_stride + 1;
-  const size_t in_bytes = (count * sizeof(float2) + 15) & ~(size_t)15;
-  const size_t out_bytes = (size_t)outs * (size_t)d->K * sizeof(float);
-  rc = grow(p, d->stage, in_bytes + out_bytes, "demod staging");
-  if (!rc) rc = use_stream(p, p->stream);  // the staging may still be read by the previous call
-  if (rc) return rc;
-  char *dev = d->stage.as<char>();
-  hipError_t e = hipMemcpyAsync(dev, x, count * sizeof(float2), hipMemcpyHostToDevice, p->stream);
-  if (e != hipSuccess) return hip_fail(e, "H2D samples");
-  rc = zfft_demod_push_device(p, dev, steps, step_stride, stream_stride, dev + in_bytes, p->stream);
-  if (rc) return rc;
-  e = out_bytes ? hipMemcpyAsync(out, dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, p->stream) : hipSuccess;
-  return sync_read(p, e, "demod push");
+  return stream_host_push(p, d->s, kNames, x, count * sizeof(float2), out, (size_t)outs * (size_t)d->K * sizeof(float),
+                          [=](const void *d_in, void *d_out) {
+                            return push_on(p, d_in, steps, step_stride, stream_stride, d_out, p->stream);
+                          });
 }
 
 int zfft_demod_state(zfft_plan *p, uint64_t *steps_seen) {
   if (!p || !steps_seen) return fail(ZFFT_EINVAL, "null argument");
   int rc = need_on(p);
-  if (rc) return rc;
-  *steps_seen = p->demod->n;
-  return ZFFT_OK;
+  if (!rc) *steps_seen = p->demod->s.n;
+  return rc;
 }
 
 int zfft_demod_reset(zfft_plan *p, int64_t n0) {
   int rc = enter(p);
-  if (rc) return rc;
-  rc = need_on(p);
-  if (rc) return rc;
-  if (n0 < 0 || (uint64_t)n0 > kDemodMaxCount) return fail(ZFFT_EINVAL, "demod_reset: n0 in [0, 2^62]");
-  return restart(p, (uint64_t)n0);
+  if (!rc) rc = need_on(p);
+  return rc ? rc : stream_reset(p, p->demod->s, kNames, n0);
 }
 
 int zfft_demod_info(const zfft_plan *p, double *group_delay, double *rate_ratio) {

@@ -13,8 +13,6 @@ void set_error(const std::string &msg);  // zfft_plan.cpp
 
 namespace {
 
-uint64_t ceil_div(uint64_t a, uint64_t d) { return a / d + (a % d != 0); }
-
 int lds_of(int kind, int lanes, int rows) { return 4 * lanes * (demod_row(rows - 1, kind) + 1); }
 
 // The longest span, whole output steps, whose detected values and history fit `budget` bytes.
@@ -34,11 +32,6 @@ bool demod_shape_ok(int K, int Ta, int Da) {
 bool demod_strides_ok(int K, int64_t step_stride, int64_t stream_stride) {
   return step_stride >= 1 && step_stride <= kDemodMaxStride && stream_stride >= (K > 1 ? 1 : 0) &&
          stream_stride <= kDemodMaxStride;
-}
-
-int64_t demod_steps(uint64_t n0, int64_t steps, int32_t Da) {
-  if (steps < 0 || Da < 1 || n0 > kDemodMaxCount || steps > kDemodMaxPush) return 0;
-  return (int64_t)(ceil_div(n0 + (uint64_t)steps, (uint64_t)Da) - ceil_div(n0, (uint64_t)Da));
 }
 
 DemodForm choose_demod(int K, int Ta, int Da, int64_t step_stride, int64_t stream_stride) {
@@ -72,7 +65,7 @@ DemodCut demod_cut(const DemodForm &f, uint64_t n0, int64_t steps, int Da) {
   c.nspans = (steps + f.span - 1) / f.span;
   c.ntiles = c.nspans * f.stream_tiles;
   c.outs = demod_steps(n0, steps, Da);
-  c.r0 = (int)(ceil_div(n0, (uint64_t)Da) * (uint64_t)Da - n0);
+  c.r0 = (int)stream_first(n0, Da);
   c.grid = (int)std::min<int64_t>(c.ntiles, kDemodGridMax);
   return c;
 }

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "zfft.h"
+#include "zfft_stream_plan.h"
 
 namespace zfft {
 
@@ -25,8 +26,8 @@ constexpr int kDemodLdsMax = 64 * 1024;   // ... and may take where the history 
 constexpr int kDemodCuLds = 160 * 1024;   // LDS of a CU
 constexpr int kDemodPadShift = 5;         // time form: one pad slot after every 32 detected values
 constexpr int kDemodGridMax = 1 << 16;    // workgroups of a launch: they walk the tiles round-robin
-constexpr int64_t kDemodMaxPush = INT32_MAX;            // steps of a push
-constexpr uint64_t kDemodMaxCount = (uint64_t)1 << 62;  // the bank's step count (zfft_demod_reset)
+constexpr int64_t kDemodMaxPush = kStreamMaxPush;        // steps of a push
+constexpr uint64_t kDemodMaxCount = kStreamMaxCount;     // the bank's step count (zfft_demod_reset)
 constexpr int64_t kDemodMaxStride = (int64_t)1 << 31;   // either stride, in complex samples
 
 enum DemodKind {
@@ -83,8 +84,8 @@ bool demod_shape_ok(int K, int Ta, int Da);
 bool demod_strides_ok(int K, int64_t step_stride, int64_t stream_stride);
 
 // ceil((n0 + steps) / Da) - ceil(n0 / Da): the outputs of a push of `steps` at count n0 (rule 3).
-// 0 outside steps >= 0, Da >= 1, n0 <= 2^62.
-int64_t demod_steps(uint64_t n0, int64_t steps, int32_t Da);
+// 0 outside steps >= 0, Da >= 1, n0 <= 2^62 (stream_count).
+inline int64_t demod_steps(uint64_t n0, int64_t steps, int32_t Da) { return stream_count(n0, n0, steps, Da); }
 
 // !ok() outside a valid shape and valid strides.
 DemodForm choose_demod(int K, int Ta, int Da, int64_t step_stride, int64_t stream_stride);

@@ -244,11 +244,9 @@ int zfft_detect_floors_device(zfft_plan *p, const float *d_rows, int32_t count, 
   rc = need_local(p);
   if (rc) return rc;
   if (!d_rows || !d_floors || count < 1 || count > kMaxDetectRows) return fail(ZFFT_EINVAL, "bad rows / output / count");
-  hipStream_t st = pick_stream(p, hip_stream);
-  rc = use_stream(p, st);
+  hipStream_t st;
+  rc = begin_call(p, hip_stream, &st);
   if (rc) return rc;
-  p->n_marks = 0;
-  mark(p, st, "start");
   // straight into the caller's rows: no scratch; the cap only sets the rows of a launch
   rc = run_floors(p, d_rows, count, d_floors, p->cfg.n_win, p->dt_local_cap, st);
   if (rc) return rc;

@@ -104,11 +104,9 @@ int zfft_history_push_device(zfft_plan *p, const float *d_rows, int32_t count, v
   if (!d_rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
   // a push longer than the ring keeps its last hs_cap rows
   const int64_t skip = std::max<int64_t>(0, (int64_t)count - p->hs_cap);
-  hipStream_t st = pick_stream(p, hip_stream);
-  rc = use_stream(p, st);
+  hipStream_t st;
+  rc = begin_call(p, hip_stream, &st);
   if (rc) return rc;
-  p->n_marks = 0;
-  mark(p, st, "start");
   hipError_t e = launch_history_pack(d_rows + skip * p->cfg.n_win, p->cfg.n_win, (int)(count - skip),
                                      (int64_t)p->hs_seen + skip, store_of(p), st);
   if (e != hipSuccess) return hip_fail(e, "history push");
@@ -148,11 +146,9 @@ int zfft_history_read_device(zfft_plan *p, int64_t first, int32_t count, float *
   if (!d_rows || count < 1 || count > kMaxPushRows) return fail(ZFFT_EINVAL, "bad rows / count");
   if (first < 0 || (uint64_t)first < oldest_of(p) || (uint64_t)first + (uint64_t)count > p->hs_seen)
     return fail(ZFFT_EINVAL, "history read: rows outside [oldest, rows_seen)");
-  hipStream_t st = pick_stream(p, hip_stream);
-  rc = use_stream(p, st);
+  hipStream_t st;
+  rc = begin_call(p, hip_stream, &st);
   if (rc) return rc;
-  p->n_marks = 0;
-  mark(p, st, "start");
   hipError_t e = launch_history_unpack(store_of(p), first, count, p->cfg.n_win, d_rows, st);
   if (e != hipSuccess) return hip_fail(e, "history read");
   mark(p, st, "history_unpack");
@@ -204,11 +200,9 @@ int zfft_history_view_device(zfft_plan *p, const zfft_history_window *w, float *
   if (!f.ok()) return fail(ZFFT_EINTERNAL, "history: no form for this window");
   rc = grow(p, p->hs_scratch, history_scratch_bytes(f, g.width), "history scratch");
   if (rc) return rc;
-  hipStream_t st = pick_stream(p, hip_stream);
-  rc = use_stream(p, st);
+  hipStream_t st;
+  rc = begin_call(p, hip_stream, &st);
   if (rc) return rc;
-  p->n_marks = 0;
-  mark(p, st, "start");
   const HistStore s = store_of(p);
   hipError_t e = launch_history_view(s, g, f, d_img, p->hs_scratch.p, p->hs_scratch.cap, st);
   if (e != hipSuccess) return hip_fail(e, "history view");

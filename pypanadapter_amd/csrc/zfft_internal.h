@@ -1,9 +1,10 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
 // zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp,
-// zfft_history.cpp, zfft_tap.cpp, the table builders xa_tables.cpp and pc_tables.cpp) and the HIP kernels
+// zfft_history.cpp, zfft_stream.cpp, zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp, the table builders
+// xa_tables.cpp and pc_tables.cpp) and the HIP kernels
 // (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, fc2_kernels.hip,
 // detect_kernels.hip, detect_local_kernels.hip, track_kernels.hip, view_kernels.hip,
-// history_kernels.hip, tap_kernels.hip).  Not part of the C-ABI.
+// history_kernels.hip, tap_kernels.hip, chan_kernels.hip, demod_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -69,6 +69,14 @@ int use_stream(zfft_plan *p, hipStream_t st) {
   }
   return ZFFT_OK;
 }
+int begin_call(zfft_plan *p, void *hip_stream, hipStream_t *st) {
+  *st = pick_stream(p, hip_stream);
+  int rc = use_stream(p, *st);
+  if (rc) return rc;
+  p->n_marks = 0;
+  mark(p, *st, "start");
+  return ZFFT_OK;
+}
 int done_on(zfft_plan *p, hipStream_t st) {
   hipError_t e = hipEventRecord(p->done_ev, st);
   if (e != hipSuccess) return hip_fail(e, "hipEventRecord");

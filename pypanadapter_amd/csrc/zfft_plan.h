@@ -1,7 +1,7 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
-// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp).  Not part of
-// the C-ABI.
+// zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_stream.cpp,
+// zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 
 namespace zfft {
 
+struct TapState;   // zfft_tap.cpp
 struct ChanState;  // zfft_chan.cpp
 struct DemodState;  // zfft_demod.cpp
 
@@ -165,25 +166,8 @@ struct zfft_plan {
   uint64_t hs_seen = 0;
   int hs_kind = 0;                 // HistForm::kind of the last view (test hook zfft__plan_history_form)
   DevBuf hs_store, hs_img, hs_rgba, hs_scratch, hs_replay;
-  // channel taps (zfft_plan_taps; zfft_tap.cpp): tp_max = max_taps, 0 = off (no buffer).  tp_tab
-  // holds a row of tp_len entries c[k] per slot, tp_carry two carries of tp_len - 1 samples (a
-  // push reads the one of parity tp_par and writes the other), tp_stage the device staging of
-  // zfft_tap_push, tp_pin the page-locked staging of the slots' table uploads (tp_dirty: a slot's
-  // part may still be read by an enqueued copy).  tp_n counts the samples given (host side:
-  // pushes are in call order), tp_slots the open taps
-  int tp_max = 0, tp_len = 0, tp_par = 0;
-  int tp_layout = 0;               // hook zfft__plan_tap_layout: 0 = the chooser's staging layout
-  uint64_t tp_n = 0;
-  struct TapSlot {
-    bool open = false;
-    int64_t fw = 0;
-    int32_t D = 0, T = 0;
-    uint64_t n_open = 0;
-  };
-  std::vector<TapSlot> tp_slots;
-  std::vector<char> tp_dirty;
-  DevBuf tp_tab, tp_carry, tp_stage;
-  float2 *tp_pin = nullptr;
+  // channel taps (zfft_plan_taps; zfft_tap.cpp): null = off (nothing allocated); the state is that file's
+  zfft::TapState *tap = nullptr;
   // channeliser (zfft_plan_chan; zfft_chan.cpp): null = off (nothing allocated); the state is that file's
   zfft::ChanState *chan = nullptr;
   // demodulator bank (zfft_plan_demod; zfft_demod.cpp): null = off (nothing allocated); the state is that file's
@@ -218,6 +202,9 @@ int hip_fail(hipError_t e, const char *where);
 void mark(zfft_plan *p, hipStream_t st, const char *what = "");
 // Order `st` after everything the plan enqueued before (on any stream).
 int use_stream(zfft_plan *p, hipStream_t st);
+// Opens a device call on the caller's stream handle: *st = that stream, ordered after the plan's
+// earlier work (use_stream), the timing marks restarted with "start" on it.
+int begin_call(zfft_plan *p, void *hip_stream, hipStream_t *st);
 // Mark the end of the plan's work enqueued so far on `st`.
 int done_on(zfft_plan *p, hipStream_t st);
 // Wait on the host until the plan's enqueued work is done (before a synchronous upload

@@ -16,21 +16,12 @@ void set_error(const std::string &msg);  // zfft_plan.cpp
 
 namespace {
 
-uint64_t ceil_div(uint64_t a, uint64_t d) { return a / d + (a % d != 0); }
-
 int tap_fail(const char *msg) {
   set_error(msg);
   return ZFFT_EINVAL;
 }
 
 }  // namespace
-
-int64_t tap_count(uint64_t n0, uint64_t n_open, int64_t n, int32_t D) {
-  if (n < 0 || D < 1 || n0 > kTapMaxCount || n > kTapMaxPush) return 0;
-  const uint64_t a = std::max(n0, n_open), end = n0 + (uint64_t)n;
-  if (a >= end) return 0;
-  return (int64_t)(ceil_div(end, (uint64_t)D) - ceil_div(a, (uint64_t)D));
-}
 
 int tap_conflict(int D, int shift) {
   int sum = 0;
@@ -90,8 +81,8 @@ TapForm choose_tap(uint64_t n0, int64_t n, int max_len, const TapOpen *taps, int
   for (int i = 0; i < ntaps; ++i) {
     const TapOpen &t = taps[i];
     TapItem &it = items->t[i];
-    const uint64_t first = ceil_div(n0, (uint64_t)t.D) * (uint64_t)t.D;  // m D of the first output: n_open <= n0
-    it.r0 = (int64_t)(first - n0);
+    it.r0 = (int64_t)stream_first(n0, t.D);
+    const uint64_t first = n0 + (uint64_t)it.r0;  // m D of the first output: n_open <= n0
     it.count = (int32_t)tap_count(n0, t.n_open, n, t.D);
     it.out_off = off;
     // the phase words wrap at 2^32 exactly: unsigned 32-bit products of the low words

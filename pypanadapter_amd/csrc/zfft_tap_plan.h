@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "zfft.h"
+#include "zfft_stream_plan.h"
 
 namespace zfft {
 
@@ -21,8 +22,8 @@ constexpr int kTapSpanMax = 4096;     // input samples a workgroup owns, at most
 constexpr int kTapSpanMin = 512;      // ... and at least (a short push spreads over more of the chip)
 constexpr int kTapSpansWanted = 1024; // workgroups a push should give before the span grows
 constexpr int kTapLdsMax = 64 * 1024; // bytes of LDS a launch may ask for without an attribute
-constexpr int64_t kTapMaxPush = INT32_MAX;             // samples of a push
-constexpr uint64_t kTapMaxCount = (uint64_t)1 << 62;   // the plan's sample count (zfft_tap_reset)
+constexpr int64_t kTapMaxPush = kStreamMaxPush;       // samples of a push
+constexpr uint64_t kTapMaxCount = kStreamMaxCount;    // the plan's sample count (zfft_tap_reset)
 
 #if defined(__HIPCC__)
 #define ZFFT_TAP_HD __host__ __device__
@@ -86,8 +87,8 @@ struct TapForm {
 };
 
 // ceil((n0 + n) / D) - ceil(max(n0, n_open) / D): the outputs of a tap in a push of n samples at
-// count n0 (the rule's clause on counts).  0 outside n >= 0, D >= 1.
-int64_t tap_count(uint64_t n0, uint64_t n_open, int64_t n, int32_t D);
+// count n0 (the rule's clause on counts; stream_count).  0 outside n >= 0, D >= 1.
+inline int64_t tap_count(uint64_t n0, uint64_t n_open, int64_t n, int32_t D) { return stream_count(n0, n_open, n, D); }
 
 // The form of a push of n samples at count n0 on a plan of max_len, and the items of its open
 // taps (slot order as given; offsets the prefix sums of the counts).  !ok() outside 1 <= n <= 2^31 - 1,

@@ -133,11 +133,9 @@ int zfft_track_push_device(zfft_plan *p, const int32_t *d_found, const zfft_emis
   const int rows0 = std::min(count, f.pass_rows);
   rc = grow(p, p->tk_scratch, track_scratch_bytes(K, gap, rows0), "track scratch");
   if (rc) return rc;
-  hipStream_t st = pick_stream(p, hip_stream);
-  rc = use_stream(p, st);
+  hipStream_t st;
+  rc = begin_call(p, hip_stream, &st);
   if (rc) return rc;
-  p->n_marks = 0;
-  mark(p, st, "start");
   TrackArgs a = base_args(p);
   for (int off = 0; off < count; off += f.pass_rows) {  // (one stream: a pass reuses the scratch after the last)
     a.R = std::min(f.pass_rows, count - off);

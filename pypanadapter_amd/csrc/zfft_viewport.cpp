@@ -122,11 +122,9 @@ int zfft_viewport_push_device(zfft_plan *p, const float *d_rows, int32_t count, 
   g.direct = view_direct(g, f) ? 1 : 0;
   rc = grow(p, p->vw_scratch, view_scratch_bytes(f, g.width), "viewport scratch");
   if (rc) return rc;
-  hipStream_t st = pick_stream(p, hip_stream);
-  rc = use_stream(p, st);  // after the fills and earlier pushes, on any stream
+  hipStream_t st;
+  rc = begin_call(p, hip_stream, &st);  // after the fills and earlier pushes, on any stream
   if (rc) return rc;
-  p->n_marks = 0;
-  mark(p, st, "start");
   hipError_t e = launch_view_lines(d_rows, g, f, p->vw_ring.as<float>(), p->vw_tr.as<float>(), p->vw_scratch.p,
                                    p->vw_scratch.cap, st);
   if (e != hipSuccess) return hip_fail(e, "viewport push");

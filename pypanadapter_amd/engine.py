@@ -644,9 +644,21 @@ class ZoomFFT:
         check(self.lib.zfft_tap_shape(self._plan, ctypes.byref(m), ctypes.byref(n)), "zfft_tap_shape")
         return m.value, n.value
 
+    @staticmethod
+    def _phase_word(f_hz: float, rate: float) -> int:
+        """round(f_hz / rate * 2^32), wrapped into [-2^31, 2^31): the taps' and the bank's frequency words."""
+        return (int(round(float(f_hz) / rate * 2.0 ** 32)) + 2 ** 31) % 2 ** 32 - 2 ** 31
+
+    def _stretch(self, x, who: str):
+        """A host push's 1-D stretch of samples in the plan's input format, and its sample count."""
+        x = self._as_iq(x)
+        if x.ndim != 1:
+            raise ValueError(f"{who} takes a 1-D stretch of samples")
+        return x, self._samples(x)
+
     def tap_freq_word(self, f_hz: float) -> int:
         """The freq_word nearest f_hz: round(f_hz / fs * 2^32), wrapped into [-2^31, 2^31)."""
-        return (int(round(float(f_hz) / self.fs * 2.0 ** 32)) + 2 ** 31) % 2 ** 32 - 2 ** 31
+        return self._phase_word(f_hz, self.fs)
 
     def tap_open(self, slot: int, f_hz: float, decim: int, taps=None, cutoff: float | None = None,
                  beta: float = 8.0) -> float:
@@ -694,10 +706,7 @@ class ZoomFFT:
     def tap_push(self, x) -> list:
         """The next samples of the stream (1-D, the plan's input format) from the host; returns
         one complex64 array per open slot, in slot order.  Synchronous."""
-        x = self._as_iq(x)
-        if x.ndim != 1:
-            raise ValueError("tap_push takes a 1-D stretch of samples")
-        n = self._samples(x)
+        x, n = self._stretch(x, "tap_push")
         counts = self.tap_counts(n)
         out = np.empty(int(counts.sum()), dtype=np.complex64)
         check(self.lib.zfft_tap_push(self._plan, x.ctypes.data_as(ctypes.c_void_p), n,
@@ -764,10 +773,7 @@ class ZoomFFT:
     def chan_push(self, x) -> np.ndarray:
         """The next samples of the stream (1-D, the plan's input format) from the host; returns a
         (steps, c_count) complex64 array, one row per output step.  Synchronous."""
-        x = self._as_iq(x)
-        if x.ndim != 1:
-            raise ValueError("chan_push takes a 1-D stretch of samples")
-        n = self._samples(x)
+        x, n = self._stretch(x, "chan_push")
         out = np.empty((self.chan_steps(n), self.chan_shape()[4]), dtype=np.complex64)
         check(self.lib.zfft_chan_push(self._plan, x.ctypes.data_as(ctypes.c_void_p), n,
                                       out.ctypes.data_as(ctypes.c_void_p), None), "zfft_chan_push")
@@ -839,7 +845,7 @@ class ZoomFFT:
         window included."""
         m = self.DEMOD_MODES[mode.lower()] if isinstance(mode, str) else int(mode)
         rate = self.fs if rate is None else float(rate)
-        word = (int(round(float(bfo_hz) / rate * 2.0 ** 32)) + 2 ** 31) % 2 ** 32 - 2 ** 31
+        word = self._phase_word(bfo_hz, rate)
         if count is None:
             count = self.demod_shape()[0] - int(first)
         check(self.lib.zfft_demod_mode(self._plan, int(first), int(count), m, word), "zfft_demod_mode")

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "zfft_chan_plan.h"
+#include "zfft_tap_plan.h"
 
 namespace zfft {
 void set_error(const std::string &) {}
@@ -67,6 +68,9 @@ int main() {
               check(f.ok() == in_domain, "the domain", M, P, D);
               check(chan_shape_ok(M, P, D) == (P >= 1 && P <= kChanMaxLen / M && (D == M || D == M / 2)), "shape_ok", M, P, D);
               ++keys;
+              // one rule for every producer: the steps are the shared count, and a tap's that was open before the push
+              check(chan_steps(n0, n, D) == stream_count(n0, n0, n, D) && tap_count(n0, n0 / 2, n, D) == chan_steps(n0, n, D),
+                    "the shared count", (long long)n0, n, D);
               if (!f.ok()) continue;
               const int T = M * P;
               check(f.points == 4096 || f.points == 2048 || f.points == 1024, "points", M, P, f.points);

@@ -13,7 +13,9 @@
 #include <string>
 #include <vector>
 
+#include "zfft_chan_plan.h"
 #include "zfft_demod_plan.h"
+#include "zfft_tap_plan.h"
 
 namespace zfft {
 void set_error(const std::string &) {}
@@ -73,6 +75,9 @@ int main() {
               check(c.r0 >= 0 && c.r0 < Da && (n0 + (uint64_t)c.r0) % (uint64_t)Da == 0, "first output", K, Da, c.r0);
               check(c.outs == (int64_t)(cdiv(n0 + (uint64_t)n, (uint64_t)Da) - m0) && c.outs == demod_steps(n0, n, Da), "outputs", K, Da,
                     (long long)c.outs);
+              // one rule for every producer: the outputs are the shared count, and a tap's that was open before the push
+              check(demod_steps(n0, n, Da) == stream_count(n0, n0, n, Da) && tap_count(n0, n0 / 2, n, Da) == chan_steps(n0, n, Da),
+                    "the shared count", (long long)n0, (long long)n, Da);
               if (c.nspans > 512) continue;  // (the walk below span by span, on pushes of moderate length)
               int64_t next = 0;
               for (int64_t b = 0; b < c.nspans; ++b) {

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "zfft_chan_plan.h"
 #include "zfft_tap_plan.h"
 
 namespace zfft {
@@ -52,6 +53,8 @@ int main() {
           const uint64_t a = n_open > n0 ? n_open : n0;
           check(c == (int64_t)(cdiv(n0 + (uint64_t)n, (uint64_t)D) - cdiv(a, (uint64_t)D)), "the count's formula",
                 (long long)n0, n, D);
+          // one rule for every producer: the taps' count is the shared one, and the channeliser's once the tap is open
+          check(c == stream_count(n0, n_open, n, D) && c == chan_steps(n0, n, D), "the shared count", (long long)n0, n, D);
           ++keys;
         }
   check(tap_count(10, 50, 20, 4) == 0 && tap_count(10, 29, 20, 4) == 0 && tap_count(10, 28, 20, 4) == 1, "opened late in the push",
