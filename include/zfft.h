@@ -956,6 +956,78 @@ int zfft_demod_info(const zfft_plan *plan, double *group_delay, double *rate_rat
 /* No plan, no GPU.  zfft_tap_design for n_taps in [1, 1024]. */
 int zfft_demod_design(int32_t n_taps, double cutoff, double beta, double *h_out);
 
+/* Resampler bank: K real float32 lanes on the device at L / M times their rate -- the
+ * demodulator's audio at a rate a sound device takes, or a complex stream (two lanes) at the rate
+ * a decoder wants -- as float32 or as int16 PCM.  Off by default: a plan that never calls
+ * zfft_plan_resamp allocates and launches nothing.  The rule (reference: tests/resamp_ref.py):
+ *   0. input: float32 on the device, time-major: lane s at step n is x[n step_stride + s], s < K,
+ *      1 <= K <= 2048, step_stride in floats in [K, 2^31].  zfft_demod_push_device's output is
+ *      (K, step_stride) = (streams, streams).  A complex stream is two lanes: one tap's output is
+ *      K = 2, step_stride = 2, the channeliser's (steps, channels) complex64 is K = step_stride =
+ *      2 channels.  Nothing is copied or transposed: a subset of neighbouring lanes is read in
+ *      place by offsetting the pointer and keeping the stride.
+ *   1. ratio: L outputs per M inputs, 1 <= L <= 512, 1 <= M <= 4096, gcd(L, M) = 1 (anything else
+ *      is ZFFT_EINVAL); T taps per phase, 1 <= T <= 128, L T <= 8192; one real float32 prototype
+ *      h[0 .. T L) at the upsampled rate, shared by all lanes.
+ *   2. count: the bank counts input steps n = 0, 1, ... from zfft_plan_resamp, or from
+ *      zfft_resamp_reset(plan, n0), which restarts the count at n0 (0 <= n0 <= 2^62) and zeroes the
+ *      carry; x_s[n] = 0 before the start.  The count and the carry are the bank's own, independent
+ *      of the taps', the channeliser's and the demodulator's.  Output m sits at input time m M / L:
+ *      its input index is i_m = floor(m M / L), its phase p_m = m M mod L, and
+ *        y[m, s] = sum_{k < T} h[k L + p_m] x_s[i_m - k]
+ *      -- scipy.signal.upfirdn(h, x, L, M) on an absolute time axis.  The sum's order is fixed:
+ *      four partial sums a_j over the k = j (mod 4) in ascending k, one fused multiply-add each,
+ *      then (a_0 + a_1) + (a_2 + a_3).  Exactly T products are formed per output.
+ *   3. push: a push of `steps` at count n0 emits the m with n0 <= i_m < n0 + steps:
+ *      ceil((n0 + steps) L / M) - ceil(n0 L / M) of them (zfft_resamp_steps, for the next push; a
+ *      pure host function in 128-bit arithmetic, n0 L reaching 2^71).  Output is time-major,
+ *      out[j K + s] for output j of the push.
+ *   4. format: ZFFT_RESAMP_F32 writes y.  ZFFT_RESAMP_S16 writes the int16
+ *      q = clamp(rint(y scale), -32768, 32767): one rounded float32 product with the float32
+ *      `scale` of the enable (32767 is the usual one, for |y| <= 1), rint to nearest with ties to
+ *      even; NaN gives 0 and +-inf saturate.
+ *   5. carry: the bank carries the last T - 1 input steps of every lane on the device, and the
+ *      outputs are the same bit for bit however the stream is cut into pushes, pushes shorter than
+ *      the carry included, and whichever form of the kernel runs.
+ *   6. the group delay (T L - 1) / (2 L) input steps and the rate ratio L / M are reported
+ *      (zfft_resamp_info), not compensated.  zfft_resamp_design(L, M, T, beta, h_out) is
+ *      zfft_tap_design's formula at length T L and cutoff 0.4 / max(L, M) cycles per upsampled
+ *      sample -- a symmetric Kaiser sinc of unit sum -- multiplied by L, so that every phase has
+ *      unit gain.  h = NULL means that design with T = 16 ceil(max(L, M) / L) and beta 8; where
+ *      that T breaks rule 1 the call is ZFFT_EINVAL and the caller gives taps.
+ *   7. |y - y_exact| <= (T + 32) 2^-24 sum_k |h[k L + p]| max|x|: each partial sum is at most
+ *      ceil(T / 4) rounded multiply-adds and two adds join them (rule 6 of the demodulator with
+ *      no detector term).  S16 adds half a code, and one rounding of the product.
+ * zfft_resamp_push_device is enqueued on its stream with no sync, ordered after earlier work on
+ * that stream and after the plan's earlier calls on any stream; d_out must hold zfft_resamp_steps x
+ * K elements of the format and not overlap d_x.  Every zfft_resamp_* call on a plan with the bank
+ * off returns ZFFT_EINVAL ("resamp is off"; zfft_resamp_shape after reporting zeros).  With
+ * zfft_plan_timing on a push reports its one launch as "resamp_push". */
+enum { ZFFT_RESAMP_F32 = 0, ZFFT_RESAMP_S16 = 1 };
+/* n_lanes = 0: off, frees everything.  Otherwise n_lanes, L, M, taps_per_phase as rules 0 and 1,
+ * anything else ZFFT_EINVAL; h: L taps_per_phase host floats, or NULL for rule 6's default, with
+ * taps_per_phase 0 or 16 ceil(max(L, M) / L); format ZFFT_RESAMP_*, scale used by S16 alone.  A
+ * call restarts the count at 0. */
+int zfft_plan_resamp(zfft_plan *plan, int32_t n_lanes, int32_t L, int32_t M, int32_t taps_per_phase, const float *h,
+                     int32_t format, float scale);
+int zfft_resamp_shape(const zfft_plan *plan, int32_t *n_lanes, int32_t *L, int32_t *M, int32_t *taps_per_phase,
+                      int32_t *format);
+/* the outputs a push of `steps` (0 .. 2^31 - 1) now would emit; a pure host function of the count */
+int zfft_resamp_steps(const zfft_plan *plan, int64_t steps, int64_t *outputs);
+/* steps (1 .. 2^31 - 1; 0 is ZFFT_OK and does nothing) of the K lanes on the device, rule 0 */
+int zfft_resamp_push_device(zfft_plan *plan, const void *d_x, int64_t steps, int64_t step_stride, void *d_out,
+                            void *stream);
+/* host input ((steps - 1) step_stride + K float32) and outputs; outputs_out (or NULL) as
+ * zfft_resamp_steps before the push; synchronous */
+int zfft_resamp_push(zfft_plan *plan, const void *x, int64_t steps, int64_t step_stride, void *out,
+                     int64_t *outputs_out);
+int zfft_resamp_state(zfft_plan *plan, uint64_t *steps_seen);
+int zfft_resamp_reset(zfft_plan *plan, int64_t n0);
+/* group_delay = (T L - 1) / (2 L) input steps; rate_ratio = L / M outputs per step */
+int zfft_resamp_info(const zfft_plan *plan, double *group_delay, double *rate_ratio);
+/* No plan, no GPU.  Rule 6: L taps_per_phase float64 values. */
+int zfft_resamp_design(int32_t L, int32_t M, int32_t taps_per_phase, double beta, double *h_out);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

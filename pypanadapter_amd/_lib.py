@@ -101,6 +101,8 @@ EXPORTS = [
     "zfft_chan_push", "zfft_chan_state", "zfft_chan_reset", "zfft_chan_info", "zfft_chan_design",
     "zfft_plan_demod", "zfft_demod_shape", "zfft_demod_mode", "zfft_demod_steps", "zfft_demod_push_device",
     "zfft_demod_push", "zfft_demod_state", "zfft_demod_reset", "zfft_demod_info", "zfft_demod_design",
+    "zfft_plan_resamp", "zfft_resamp_shape", "zfft_resamp_steps", "zfft_resamp_push_device", "zfft_resamp_push",
+    "zfft_resamp_state", "zfft_resamp_reset", "zfft_resamp_info", "zfft_resamp_design",
 ]
 
 _lib = None
@@ -268,6 +270,15 @@ def load(path: str = ""):
         "zfft_demod_reset": (ctypes.c_int, [P, I64]),
         "zfft_demod_info": (ctypes.c_int, [P, ctypes.POINTER(D), ctypes.POINTER(D)]),
         "zfft_demod_design": (ctypes.c_int, [I32, D, D, P]),
+        "zfft_plan_resamp": (ctypes.c_int, [P, I32, I32, I32, I32, P, I32, ctypes.c_float]),
+        "zfft_resamp_shape": (ctypes.c_int, [P] + [ctypes.POINTER(I32)] * 5),
+        "zfft_resamp_steps": (ctypes.c_int, [P, I64, ctypes.POINTER(I64)]),
+        "zfft_resamp_push_device": (ctypes.c_int, [P, P, I64, I64, P, P]),
+        "zfft_resamp_push": (ctypes.c_int, [P, P, I64, I64, P, P]),
+        "zfft_resamp_state": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_uint64)]),
+        "zfft_resamp_reset": (ctypes.c_int, [P, I64]),
+        "zfft_resamp_info": (ctypes.c_int, [P, ctypes.POINTER(D), ctypes.POINTER(D)]),
+        "zfft_resamp_design": (ctypes.c_int, [I32, I32, I32, D, P]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

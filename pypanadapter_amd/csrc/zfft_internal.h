@@ -1,10 +1,10 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
 // zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp,
-// zfft_history.cpp, zfft_stream.cpp, zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp, the table builders
+// zfft_history.cpp, zfft_stream.cpp, zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp, zfft_resamp.cpp, the table builders
 // xa_tables.cpp and pc_tables.cpp) and the HIP kernels
 // (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, fc2_kernels.hip,
 // detect_kernels.hip, detect_local_kernels.hip, track_kernels.hip, view_kernels.hip,
-// history_kernels.hip, tap_kernels.hip, chan_kernels.hip, demod_kernels.hip).  Not part of the C-ABI.
+// history_kernels.hip, tap_kernels.hip, chan_kernels.hip, demod_kernels.hip, resamp_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 
 #include "zfft_chan_plan.h"    // the channeliser's forms (ChanForm)
 #include "zfft_demod_plan.h"   // the demodulator bank's forms (DemodForm, DemodCut)
+#include "zfft_resamp_plan.h"  // the resampler bank's forms (ResampForm, ResampCut)
 #include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
 #include "zfft_history_plan.h"  // the row history's quantiser and forms (HistQuant, HistForm)
 #include "zfft_tap_plan.h"     // the channel taps' forms and items (TapForm, TapItems)
@@ -545,6 +546,14 @@ hipError_t launch_demod_push(const float2 *x, int64_t steps, int64_t step_stride
                              hipStream_t st);
 // par[s_first .. s_first + s_count) = (mode, word), in stream order.
 hipError_t launch_demod_mode(uint32_t *par, int s_first, int s_count, uint32_t mode, uint32_t word, hipStream_t st);
+// Resampler bank (zfft.h's rule of zfft_plan_resamp; resamp_kernels.hip): one push of `steps` steps of
+// f.K float32 lanes at x[step * step_stride + lane], as choose_resamp and resamp_cut tiled it.  hp
+// holds the table phase-major, hp[phase * T + k] = h[k L + phase]; carry_old the T - 1 steps before
+// the push ([row * K + lane]), carry_new those before the next; out[j * K + lane], float32 or (S16)
+// int16 of the product with `scale`.  x, out and the carries do not overlap.
+hipError_t launch_resamp_push(const float *x, int64_t steps, int64_t step_stride, const ResampForm &f, const ResampCut &c,
+                              int format, float scale, const float *hp, const float *carry_old, float *carry_new,
+                              void *out, hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

@@ -1,7 +1,7 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
 // zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_stream.cpp,
-// zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp).  Not part of the C-ABI.
+// zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp, zfft_resamp.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@ namespace zfft {
 struct TapState;   // zfft_tap.cpp
 struct ChanState;  // zfft_chan.cpp
 struct DemodState;  // zfft_demod.cpp
+struct ResampState;  // zfft_resamp.cpp
 
 // A grow-only device buffer, freed with its owner.
 struct DevBuf {
@@ -172,6 +173,8 @@ struct zfft_plan {
   zfft::ChanState *chan = nullptr;
   // demodulator bank (zfft_plan_demod; zfft_demod.cpp): null = off (nothing allocated); the state is that file's
   zfft::DemodState *demod = nullptr;
+  // resampler bank (zfft_plan_resamp; zfft_resamp.cpp): null = off (nothing allocated); the state is that file's
+  zfft::ResampState *resamp = nullptr;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the
@@ -271,6 +274,10 @@ void chan_release(zfft_plan *p);
 // --- zfft_demod.cpp ---
 // Frees the demodulator bank and switches it off (the caller has waited for the plan's work).
 void demod_release(zfft_plan *p);
+
+// --- zfft_resamp.cpp ---
+// Frees the resampler bank and switches it off (the caller has waited for the plan's work).
+void resamp_release(zfft_plan *p);
 
 // --- zfft_welch.cpp ---
 // The Welch rows (or lines) of `frames` decimated frames of Ld samples at x into d_rows, by the

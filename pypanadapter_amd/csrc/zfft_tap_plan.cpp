@@ -96,6 +96,27 @@ TapForm choose_tap(uint64_t n0, int64_t n, int max_len, const TapOpen *taps, int
   return f;
 }
 
+// The design's formula for any length (zfft_tap_design, zfft_resamp_design): arguments checked by the caller.
+int kaiser_sinc(int T, double cutoff, double beta, double *h_out) {
+  // the symmetric Kaiser of T points: the periodic one of T - 1 (zfft_window_values) and its
+  // first value again; T <= 2 is a constant window, which the normalisation removes
+  std::vector<double> w((size_t)T, 1.0);
+  if (T >= 3) {
+    if (zfft_window_values(ZFFT_WIN_KAISER, &beta, T - 1, w.data()) != ZFFT_OK) return ZFFT_EINVAL;
+    w[T - 1] = w[0];
+  }
+  const double fc = 2.0 * cutoff, alpha = 0.5 * (T - 1);  // scipy's firwin: the band edge in Nyquist units
+  double sum = 0.0;
+  for (int k = 0; k < T; ++k) {
+    const double m = (double)k - alpha, x = M_PI * fc * m;
+    const double sinc = x == 0.0 ? 1.0 : std::sin(x) / x;
+    h_out[k] = fc * sinc * w[k];
+    sum += h_out[k];
+  }
+  for (int k = 0; k < T; ++k) h_out[k] /= sum;  // unit gain at DC
+  return ZFFT_OK;
+}
+
 }  // namespace zfft
 
 using namespace zfft;
@@ -134,24 +155,7 @@ int zfft_tap_design(int32_t n_taps, double cutoff, double beta, double *h_out) {
   if (!h_out || n_taps < 1 || n_taps > kTapMaxLen || !(cutoff > 0.0 && cutoff < 0.5) || !(beta >= 0.0) ||
       !std::isfinite(beta))
     return tap_fail("tap_design: n_taps in [1, 2048], 0 < cutoff < 0.5 cycles per sample, beta >= 0");
-  const int T = n_taps;
-  // the symmetric Kaiser of T points: the periodic one of T - 1 (zfft_window_values) and its
-  // first value again; T <= 2 is a constant window, which the normalisation removes
-  std::vector<double> w((size_t)T, 1.0);
-  if (T >= 3) {
-    if (zfft_window_values(ZFFT_WIN_KAISER, &beta, T - 1, w.data()) != ZFFT_OK) return ZFFT_EINVAL;
-    w[T - 1] = w[0];
-  }
-  const double fc = 2.0 * cutoff, alpha = 0.5 * (T - 1);  // scipy's firwin: the band edge in Nyquist units
-  double sum = 0.0;
-  for (int k = 0; k < T; ++k) {
-    const double m = (double)k - alpha, x = M_PI * fc * m;
-    const double sinc = x == 0.0 ? 1.0 : std::sin(x) / x;
-    h_out[k] = fc * sinc * w[k];
-    sum += h_out[k];
-  }
-  for (int k = 0; k < T; ++k) h_out[k] /= sum;  // unit gain at DC
-  return ZFFT_OK;
+  return kaiser_sinc(n_taps, cutoff, beta, h_out);
 }
 
 int zfft_tap_table(int64_t freq_word, int32_t n_taps, const float *h, float *c_out) {

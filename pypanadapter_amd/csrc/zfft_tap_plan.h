@@ -98,4 +98,8 @@ inline int64_t tap_count(uint64_t n0, uint64_t n_open, int64_t n, int32_t D) { r
 TapForm choose_tap(uint64_t n0, int64_t n, int max_len, const TapOpen *taps, int ntaps, TapItems *items,
                    int layout = 0);
 
+// zfft_tap_design's formula at any length T >= 1 (the resampler's prototype has up to 8192 taps):
+// the symmetric Kaiser sinc of unit sum.  The caller has checked 0 < cutoff < 0.5 and beta >= 0.
+int kaiser_sinc(int T, double cutoff, double beta, double *h_out);
+
 }  // namespace zfft

@@ -8,6 +8,7 @@ synchronous C-ABI calls; device tensors (torch, on the plan's device) go through
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
@@ -898,6 +899,90 @@ class ZoomFFT:
         check(self.lib.zfft_demod_info(self._plan, ctypes.byref(gd), ctypes.byref(rr)), "zfft_demod_info")
         return {"group_delay": gd.value, "rate_ratio": rr.value}
 
+    # ---------------------------------------------------------------- resampler bank
+    RESAMP_FORMATS = {"f32": 0, "s16": 1}
+
+    def set_resamp(self, lanes: int, L: int = 1, M: int = 1, taps=None, taps_per_phase: int | None = None,
+                   format="f32", scale: float = 32767.0) -> None:
+        """Resampler bank (zfft_plan_resamp): `lanes` (at most 2048) real float32 lanes on the
+        device -- what `demod_push_device` writes, or a complex stream as two lanes -- at L / M
+        times their rate (the fraction is reduced; then L <= 512, M <= 4096), through one shared
+        real prototype `taps` of L * taps_per_phase values at the upsampled rate (None designs
+        `resamp_design(L, M, 16 * ceil(max(L, M) / L))`), as "f32" or as "s16": int16
+        clamp(rint(y * scale)).  set_resamp(0) turns it off and frees it.  A call restarts the step
+        count.  The rule is in include/zfft.h, reproducible in numpy (tests/resamp_ref.py)."""
+        if int(lanes) == 0:
+            check(self.lib.zfft_plan_resamp(self._plan, 0, 0, 0, 0, None, 0, 0.0), "zfft_plan_resamp")
+            return
+        fmt = self.RESAMP_FORMATS[format.lower()] if isinstance(format, str) else int(format)
+        g = math.gcd(int(L), int(M))
+        L, M = (int(L) // g, int(M) // g) if g else (int(L), int(M))
+        if taps is None:
+            check(self.lib.zfft_plan_resamp(self._plan, int(lanes), L, M, int(taps_per_phase or 0), None, fmt, float(scale)),
+                  "zfft_plan_resamp")
+            return
+        h = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        if taps_per_phase is None:
+            taps_per_phase = h.size // max(L, 1)
+        if h.size != L * int(taps_per_phase):
+            raise ValueError("taps: L * taps_per_phase values (L of the reduced fraction)")
+        check(self.lib.zfft_plan_resamp(self._plan, int(lanes), L, M, int(taps_per_phase), h.ctypes.data_as(ctypes.c_void_p),
+                                        fmt, float(scale)), "zfft_plan_resamp")
+
+    def resamp_shape(self):
+        """(lanes, L, M, taps_per_phase, format)."""
+        v = [ctypes.c_int32() for _ in range(5)]
+        check(self.lib.zfft_resamp_shape(self._plan, *[ctypes.byref(x) for x in v]), "zfft_resamp_shape")
+        return tuple(x.value for x in v)
+
+    def resamp_steps(self, steps: int) -> int:
+        """Outputs of a push of `steps` steps now."""
+        v = ctypes.c_int64()
+        check(self.lib.zfft_resamp_steps(self._plan, int(steps), ctypes.byref(v)), "zfft_resamp_steps")
+        return v.value
+
+    def resamp_push(self, x) -> np.ndarray:
+        """The next steps of the lanes from the host: (steps, lanes) float32 (1-D for one lane), or
+        (steps, lanes / 2) complex64 (1-D for two lanes); returns (outputs, lanes) float32 or int16,
+        or (outputs, lanes / 2) complex64 for complex input of a float32 bank.  Synchronous."""
+        k, _, _, _, fmt = self.resamp_shape()
+        x = np.asarray(x)
+        cplx = np.iscomplexobj(x)
+        x = np.ascontiguousarray(x, dtype=np.complex64 if cplx else np.float32)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        if x.ndim != 2 or x.shape[1] * (2 if cplx else 1) != k:
+            raise ValueError("resamp_push takes (steps, lanes) float32 or (steps, lanes / 2) complex64")
+        out = np.empty((self.resamp_steps(x.shape[0]), k), dtype=np.int16 if fmt == 1 else np.float32)
+        check(self.lib.zfft_resamp_push(self._plan, x.ctypes.data_as(ctypes.c_void_p), x.shape[0], k,
+                                        out.ctypes.data_as(ctypes.c_void_p), None), "zfft_resamp_push")
+        return out.view(np.complex64) if cplx and fmt == 0 else out
+
+    def resamp_push_device(self, d_x_ptr: int, steps: int, step_stride: int, d_out_ptr: int, stream: int = 0) -> None:
+        """`steps` steps on the device, lane s at step n at float32 index n * step_stride + s
+        ((streams, streams) for demod_push_device's output); resamp_steps(steps) x lanes float32 or
+        int16 into d_out_ptr; enqueued on `stream`, no sync."""
+        check(self.lib.zfft_resamp_push_device(self._plan, ctypes.c_void_p(d_x_ptr), int(steps), int(step_stride),
+                                               ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream or None)),
+              "zfft_resamp_push_device")
+
+    def resamp_state(self) -> int:
+        """The steps counted so far."""
+        v = ctypes.c_uint64()
+        check(self.lib.zfft_resamp_state(self._plan, ctypes.byref(v)), "zfft_resamp_state")
+        return v.value
+
+    def resamp_reset(self, n0: int = 0) -> None:
+        """Restart the step count at n0 with an all-zero past; the shape and the taps stay."""
+        check(self.lib.zfft_resamp_reset(self._plan, int(n0)), "zfft_resamp_reset")
+
+    def resamp_info(self) -> dict:
+        """group_delay ((taps_per_phase * L - 1) / (2 L) input steps: reported, not compensated)
+        and rate_ratio (outputs per step, L / M)."""
+        gd, rr = ctypes.c_double(), ctypes.c_double()
+        check(self.lib.zfft_resamp_info(self._plan, ctypes.byref(gd), ctypes.byref(rr)), "zfft_resamp_info")
+        return {"group_delay": gd.value, "rate_ratio": rr.value}
+
     # ---------------------------------------------------------------- display viewport
     def set_viewport(self, height: int, width: int, col0: int = 0, col1: int | None = None,
                      detector: str = "max", rows_per_line: int = 1) -> None:
@@ -1273,6 +1358,18 @@ def demod_design(n_taps: int, cutoff: float, beta: float = 8.0) -> np.ndarray:
     out = np.empty(max(int(n_taps), 0), dtype=np.float64)
     check(_lib.load().zfft_demod_design(int(n_taps), float(cutoff), float(beta),
                                         out.ctypes.data_as(ctypes.c_void_p)), "zfft_demod_design")
+    return out
+
+
+def resamp_design(L: int, M: int, taps_per_phase: int | None = None, beta: float = 8.0) -> np.ndarray:
+    """The resampler bank's design (zfft_resamp_design; no GPU needed): tap_design's formula at
+    length L * taps_per_phase and cutoff 0.4 / max(L, M) cycles per upsampled sample, times L; L / M
+    a reduced fraction.  taps_per_phase None is the bank's default, 16 * ceil(max(L, M) / L)."""
+    if taps_per_phase is None:
+        taps_per_phase = 16 * (-(-max(int(L), int(M)) // max(int(L), 1)))
+    out = np.empty(max(int(L) * int(taps_per_phase), 0), dtype=np.float64)
+    check(_lib.load().zfft_resamp_design(int(L), int(M), int(taps_per_phase), float(beta),
+                                         out.ctypes.data_as(ctypes.c_void_p)), "zfft_resamp_design")
     return out
 
 

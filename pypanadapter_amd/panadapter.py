@@ -18,6 +18,7 @@ whenever (N, zoom, W, window, fs, f_lo) change (S:1753-1757, 2079-2086, 1358-136
 from __future__ import annotations
 
 import threading
+from fractions import Fraction
 
 import numpy as np
 
@@ -902,6 +903,77 @@ class Demodulator:
 
     def reset(self, n0: int = 0) -> None:
         self._plan.demod_reset(n0)
+
+
+class Resampler:
+    """What a `Demodulator`, a `Tap` or a `Channelizer` pushes at a rate a device takes, on the
+    device (ZoomFFT.set_resamp; the rule is in include/zfft.h): `lanes` real lanes -- a complex
+    stream is two -- at rate_out / rate_in = L / M times their rate through one polyphase filter,
+    with its state kept from push to push, as float32 or as int16 PCM.
+
+        audio = Demodulator.for_channelizer(bank, "fm", audio_decim=4)      # 18.75 kHz
+        pcm = Resampler.for_demodulator(audio, 48e3, format="s16")          # 64 / 25
+        s = pcm.push(audio.push(bank.push(chunk)))                           # (outputs, 64) int16 at pcm.rate
+
+    The ratio is reduced to lowest terms and must then have L <= 512 and M <= 4096 (a ValueError
+    names it otherwise).  The bank lives on its source's plan, so a caller who keeps the source's
+    output on the device can hand it to `plan.resamp_push_device` with no copy.  The group delay is
+    reported, not compensated."""
+
+    def __init__(self, plan, lanes: int, rate_in: float, rate_out: float, taps=None, taps_per_phase: int | None = None,
+                 format: str = "f32", scale: float = 32767.0):
+        self._plan, self.lanes, self.rate_in = plan, int(lanes), Fraction(rate_in)
+        ratio = Fraction(rate_out) / self.rate_in
+        self.L, self.M = ratio.numerator, ratio.denominator
+        if not (1 <= self.L <= 512 and 1 <= self.M <= 4096):
+            raise ValueError(f"rate_out / rate_in reduces to L / M = {self.L} / {self.M}: outside L <= 512, M <= 4096")
+        plan.set_resamp(self.lanes, self.L, self.M, taps=taps, taps_per_phase=taps_per_phase, format=format, scale=scale)
+
+    @classmethod
+    def for_demodulator(cls, demod: "Demodulator", rate_out: float, format: str = "f32", **kw):
+        """One lane per stream of `demod`; `push` takes what `demod.push` returns."""
+        info = demod._plan.demod_shape()
+        return cls(demod._plan, info[0], Fraction(demod.rate_in) / info[2], rate_out, format=format, **kw)
+
+    @classmethod
+    def for_tap(cls, tap: "Tap", rate_out: float, slot: int | None = None, **kw):
+        """Complex in, complex out: the open tap in `slot` (default: the only open one) as two
+        lanes; `push` takes that slot's array of `tap.push` and returns complex64."""
+        if slot is None:
+            (slot,) = tap._plan.tap_open_slots()
+        return cls(tap._plan, 2, Fraction(tap.fs) / tap._plan.tap_info(slot)["decim"], rate_out, **kw)
+
+    def close(self):
+        """Turns the bank off on the source's plan, which stays the source's."""
+        if self._plan is not None:
+            if self._plan._plan.value:  # (the source may have closed its plan already)
+                self._plan.set_resamp(0)
+            self._plan = None
+
+    @property
+    def rate(self) -> float:
+        """The output rate in Hz, exactly rate_in * L / M."""
+        return float(self.rate_in * self.L / self.M)
+
+    @property
+    def group_delay(self) -> float:
+        """(taps_per_phase * L - 1) / (2 L) input steps."""
+        return self._plan.resamp_info()["group_delay"]
+
+    def steps(self, n: int) -> int:
+        return self._plan.resamp_steps(n)
+
+    def push(self, y) -> np.ndarray:
+        """(outputs, lanes) float32 or int16 for the next (steps, lanes) float32 of the source;
+        complex64 in gives complex64 out (float32 format)."""
+        return self._plan.resamp_push(y)
+
+    @property
+    def steps_seen(self) -> int:
+        return self._plan.resamp_state()
+
+    def reset(self, n0: int = 0) -> None:
+        self._plan.resamp_reset(n0)
 
 
 class Data:
