@@ -18,8 +18,8 @@
 // g'[k] = g[k] e^(2 pi i f_lo k / fs) (lo[n] = sqrt 2 e^(-2 pi i f_lo n / fs) is an exact
 // exponential), so C holds the modulated filter's spectrum (one table per LO row) and each output
 // takes lo[8m] once, as the composite lo[6656 b] lo[8 (j - 96)] / sqrt 2.
-// Frame ends: the walk's maps (pc_edge_v beside this kernel on the side stream, pc_edge_u after
-// the join: exact minus the zero-extended model), which g's truncation changes by < 2e-8.
+// Frame ends: the walk's maps (pc_edge_batch_kernel behind this kernel on its stream: exact
+// minus the zero-extended model), which g's truncation changes by < 2e-8.
 //
 // Work per input sample: ~30 VALU lane-instructions (the walk: 74); LDS: two
 // exchanges of the 8192-point window plus three small ones of the 1024-point inverse per block

@@ -15,6 +15,8 @@
 // (own rate 276 / 438 samples, output rate 64) instead of state across tiles, so every tile and
 // every K1 tile is independent.
 // Intermediates: only y2 (rate 1/4, 8 B per 4 input samples) goes through device memory.
+#include <type_traits>
+
 #include "zfft_device.h"
 #include "zfft_pairs.h"
 
@@ -990,55 +992,96 @@ __global__ void __launch_bounds__(256) pc_edge_kernel(InDesc in, const v2f *lo, 
   }
 }
 
-// K3 split for the walk: KV makes v = V^T x for every frame end on a side
-// stream while the walk runs -- one wave per (frame, side, 4 ranks), no LDS and few VGPRs, so its
-// waves fit beside the walk's two workgroups per CU and use issue slots the walk leaves idle --
-// and KU adds U v to the walk's output once both are done (a tiny launch).  Same sums as K3.
-constexpr int kEdgeRanksPerWave = 4;
+// The frame ends of the walk and of FC, after the decimator on its stream: one workgroup per
+// (kEdgeFT frames, side).  Wave w makes v[k] = sum_j V[j][k] x[j] of ranks k = 4 w .. 4 w + 3 for
+// each of its frames -- one V value, loaded once, serves them all -- with one partial sum per
+// lane over j = lane, lane + 64, ... and the xor butterfly, and leaves v in LDS; thread t < R
+// then adds sum_k U[t][k] v[k] to output t of every frame, its U row held in registers.  A
+// frame's sums do not depend on which frames share its workgroup.  K3's own order of summation
+// (four partial sums per rank) differs, so the tile paths keep K3.
+#ifndef PC_EDGE_FT
+#define PC_EDGE_FT 4  // 2 and 8 measured: profiles/edge_batch
+#endif
+constexpr int kEdgeRanksPerWave = 4, kEdgeFT = PC_EDGE_FT;
+static_assert(kEdgeRanksPerWave * 4 == kPcEdgeRank && kPcEdgeR <= 256, "four waves take the ranks, 256 threads the outputs");
 template <int DT, int FLIP>
-__global__ void __launch_bounds__(64) pc_edge_v_kernel(InDesc in, const v2f *lo, v2f *vout,
-                                                       const float *V0, int J0, int r0,
-                                                       const float *V1, int J1, int r1) {
-  const int lane = threadIdx.x;
-  const int64_t f = blockIdx.x, L = in.len;
-  const int side = blockIdx.y, k0 = kEdgeRanksPerWave * blockIdx.z;
-  const float *V = side ? V1 : V0;
-  const int J = side ? J1 : J0, r = side ? r1 : r0;
-  if (k0 >= r) return;  // wave-uniform
-  const v2f *lor = lo_row(lo, in, f);
-  v2f acc[kEdgeRanksPerWave];
+__global__ void __launch_bounds__(256, kEdgeFT <= 4 ? 8 : 4) pc_edge_batch_kernel(InDesc in, const v2f *lo, v2f *out, int64_t n3,
+                                                            int frames, const float *U0, const float *V0,
+                                                            int R0, int J0, int r0, const float *U1,
+                                                            const float *V1, int R1, int J1, int r1) {
+  __shared__ v2f vl[kEdgeFT][kPcEdgeRank];
+  const int t = threadIdx.x, lane = t & 63, k0 = kEdgeRanksPerWave * (t >> 6);
+  const int64_t f0 = (int64_t)kEdgeFT * blockIdx.x, L = in.len;
+  const int nf = (int)(frames - f0 < kEdgeFT ? frames - f0 : kEdgeFT);  // >= 1: this call's frames only
+  const int side = blockIdx.y;
+  const float *U = side ? U1 : U0, *V = side ? V1 : V0;
+  const int R = side ? R1 : R0, J = side ? J1 : J0, r = side ? r1 : r0;
+  if (k0 < r) {  // wave-uniform
+    // The side's J samples of a frame and of its LO row as uniform bases and one 32-bit lane
+    // offset each: sample n = side ? L - 1 - j : j is element (flip ? L - 1 - n : n) of the frame.
+    constexpr int kElem = DT == kInC64 ? 8 : DT == kInCU8 ? 2 : 4;
+    const bool xrev = (side != 0) != (FLIP != 0);
+    const char *xb[kEdgeFT];
+    const v2f *lb[kEdgeFT];
+    v2f acc[kEdgeFT][kEdgeRanksPerWave];
 #pragma unroll
-  for (int k = 0; k < kEdgeRanksPerWave; ++k) acc[k] = splat(0.f);
-  for (int j = lane; j < J; j += 64) {
-    const int64_t n = side ? L - 1 - j : j;
-    const v2f x = cmul2(load_in_t<DT, FLIP>(in, f, n), lor[n]);
+    for (int i = 0; i < kEdgeFT; ++i) {
+      const int64_t f = f0 + (i < nf ? i : 0);
+      xb[i] = (const char *)in.p + (f * in.stride + (xrev ? L - J : 0)) * kElem;
+      lb[i] = lo_row(lo, in, f) + (side ? L - J : 0);
 #pragma unroll
-    for (int k = 0; k < kEdgeRanksPerWave; ++k)
-      if (k0 + k < r) acc[k] = vfma(splat(V[(int64_t)(k0 + k) * J + j]), x, acc[k]);
+      for (int k = 0; k < kEdgeRanksPerWave; ++k) acc[i][k] = splat(0.f);
+    }
+    // One trip: kEdgeFT + 5 independent loads and no branch (a slot past the call's last frame
+    // repeats frame f0 and is dropped below).  Two trips at once do not fit 64 VGPRs beside the
+    // 32 of acc (profiles/edge_batch).  rows: the plan holds several LO rows, one load per frame.
+    const auto trip = [&](unsigned j, auto rows) {
+      const unsigned jr = (unsigned)J - 1 - j, ox = xrev ? jr : j, ol = side ? jr : j;
+      float vk[kEdgeRanksPerWave];
+#pragma unroll
+      for (int k = 0; k < kEdgeRanksPerWave; ++k) vk[k] = k0 + k < r ? (V + (int64_t)(k0 + k) * J)[j] : 0.f;
+      const v2f l0 = lb[0][ol];
+#pragma unroll
+      for (int i = 0; i < kEdgeFT; ++i) {
+        const v2f l = decltype(rows)::value && i ? lb[i][ol] : l0;
+        const v2f x = cmul2(load_in_t<DT, 0>(InDesc{xb[i], 0, 0, DT, 0}, 0, ox), l);
+#pragma unroll
+        for (int k = 0; k < kEdgeRanksPerWave; ++k) acc[i][k] = vfma(splat(vk[k]), x, acc[i][k]);  // (k >= r: unused)
+      }
+    };
+    // per lane j = lane, lane + 64, ... ascending: the whole trips, then the lanes left of J mod 64
+    const auto sweep = [&](auto rows) {
+      const unsigned whole = (unsigned)J >> 6;
+      for (unsigned q = 0; q < whole; ++q) trip(64 * q + lane, rows);
+      if (64 * whole + lane < (unsigned)J) trip(64 * whole + lane, rows);
+    };
+    if (in.lo_n > 1) sweep(std::true_type{});
+    else sweep(std::false_type{});
+#pragma unroll
+    for (int i = 0; i < kEdgeFT; ++i)
+#pragma unroll
+      for (int k = 0; k < kEdgeRanksPerWave; ++k) {
+        v2f a = acc[i][k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) a += shxor(a, d);
+        if (lane == 0) vl[i][k0 + k] = a;
+      }
   }
-#pragma unroll
-  for (int k = 0; k < kEdgeRanksPerWave; ++k) {
-    v2f a = acc[k];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) a += shxor(a, d);
-    if (lane == 0 && k0 + k < r) vout[(f * 2 + side) * kPcEdgeRank + k0 + k] = a;
-  }
-}
-// out[m] += sum_k U[m][k] v[k] at both ends: one block per frame, thread t < R0 the start's
-// output t, thread 192 + t < 192 + R1 the end's output n3 - 1 - t
-__global__ void __launch_bounds__(384) pc_edge_u_kernel(const v2f *vin, v2f *out, int64_t n3,
-                                                        const float *U0, int R0, int r0,
-                                                        const float *U1, int R1, int r1) {
-  const int side = threadIdx.x >= kPcEdgeR, t = threadIdx.x - (side ? kPcEdgeR : 0);
-  const int R = side ? R1 : R0, r = side ? r1 : r0;
+  __syncthreads();
   if (t >= R) return;
-  const int64_t f = blockIdx.x;
-  const float *U = side ? U1 : U0;
-  const v2f *v = vin + (f * 2 + side) * kPcEdgeRank;
-  v2f c = splat(0.f);
-  for (int k = 0; k < r; ++k) c = vfma(splat(U[t * r + k]), v[k], c);
+  float u[kPcEdgeRank];
+#pragma unroll
+  for (int k = 0; k < kPcEdgeRank; ++k) u[k] = k < r ? U[t * r + k] : 0.f;
   const int64_t m = side ? n3 - 1 - t : t;
-  out[f * n3 + m] += c;
+#pragma unroll
+  for (int i = 0; i < kEdgeFT; ++i)
+    if (i < nf) {
+      v2f c = splat(0.f);
+#pragma unroll
+      for (int k = 0; k < kPcEdgeRank; ++k)
+        if (k < r) c = vfma(splat(u[k]), vl[i][k], c);
+      out[(f0 + i) * n3 + m] += c;
+    }
 }
 
 }  // namespace pc
@@ -1157,18 +1200,13 @@ hipError_t launch_pc_walk4(const InDesc &in, const float2 *lo, float2 *out, int6
   return hipGetLastError();
 }
 
-hipError_t launch_pc_edge_v(const InDesc &in, const float2 *lo, float2 *v, int frames,
-                            const float *const V[2], const int J[2], const int r[2], hipStream_t st) {
-  const dim3 grid(frames, 2, (kPcEdgeRank + pc::kEdgeRanksPerWave - 1) / pc::kEdgeRanksPerWave);
-  PC_DISPATCH(pc::pc_edge_v_kernel, in, grid, dim3(64), 0, st, in, (const v2f *)lo, (v2f *)v, V[0], J[0],
-              r[0], V[1], J[1], r[1]);
-  return hipGetLastError();
-}
-
-hipError_t launch_pc_edge_u(const float2 *v, float2 *out, int64_t n3, int frames, const float *const U[2],
-                            const int R[2], const int r[2], hipStream_t st) {
-  hipLaunchKernelGGL(pc::pc_edge_u_kernel, dim3(frames), dim3(2 * kPcEdgeR), 0, st, (const v2f *)v,
-                     (v2f *)out, n3, U[0], R[0], r[0], U[1], R[1], r[1]);
+hipError_t launch_pc_edge_batch(const InDesc &in, const float2 *lo, float2 *out, int64_t n3, int frames,
+                                const float *const U[2], const float *const V[2], const int R[2],
+                                const int J[2], const int r[2], hipStream_t st) {
+  if (frames <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((frames + pc::kEdgeFT - 1) / pc::kEdgeFT), 2);
+  PC_DISPATCH(pc::pc_edge_batch_kernel, in, grid, dim3(256), 0, st, in, (const v2f *)lo, (v2f *)out, n3,
+              frames, U[0], V[0], R[0], J[0], r[0], U[1], V[1], R[1], J[1], r[1]);
   return hipGetLastError();
 }
 

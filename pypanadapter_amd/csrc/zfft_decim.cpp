@@ -421,58 +421,19 @@ int run_pc8_tiles(zfft_plan *p, const InDesc &in, int frames, int64_t nd, hipStr
   return add_frame_ends(p, kPcStages, in, p->lo.as<float2>(), p->pong.as<float2>(), nd, frames, st);
 }
 
-// Work on the plan's side stream beside `st`: fork() orders side_st after st's work so far,
-// join() orders st after side_st's.  A fork left open (an error return in between) is joined
-// by the destructor, so st -- and with it the plan's done_ev -- always covers what side_st
-// was given.
-class SideFork {
- public:
-  SideFork(zfft_plan *p, hipStream_t st) : p_(p), st_(st) {}
-  SideFork(const SideFork &) = delete;
-  SideFork &operator=(const SideFork &) = delete;
-  ~SideFork() {
-    if (open_) (void)join();
-  }
-  hipError_t fork() {
-    hipError_t e = hipEventRecord(p_->fork_ev, st_);
-    if (e == hipSuccess) e = hipStreamWaitEvent(p_->side_st, p_->fork_ev, 0);
-    open_ = e == hipSuccess;
-    return e;
-  }
-  hipError_t join() {
-    open_ = false;
-    hipError_t e = hipEventRecord(p_->join_ev, p_->side_st);
-    if (e == hipSuccess) e = hipStreamWaitEvent(st_, p_->join_ev, 0);
-    return e;
-  }
-
- private:
-  zfft_plan *p_;
-  hipStream_t st_;
-  bool open_ = false;
-};
-
 // One walk or FC launch over K stages, `in` with LO table `lo` into `out` (nd samples per
-// frame), with the frame-end sums V^T x on the side stream beside it, then out += U v.  fc_tab:
-// the FC table (twiddles, then rows), or null for the walk (K = 2, 3).
+// frame), then the frame-end maps out += U (V^T x) behind it on the same stream.  fc_tab: the FC
+// table (twiddles, then rows), or null for the walk (K = 2, 3).
 int run_walk_into(zfft_plan *p, const InDesc &in, const float2 *lo, const float2 *fc_tab, int K, float2 *out,
                   int64_t nd, int frames, const char *name, hipStream_t st) {
-  hipError_t e = p->edge_v.ensure((size_t)frames * 2 * kPcEdgeRank * sizeof(float2));
-  if (e != hipSuccess) return fail(ZFFT_ENOMEM, "decimator workspace allocation failed");
-  SideFork side(p, st);
-  e = side.fork();
-  if (e != hipSuccess) return hip_fail(e, "side stream fork");
+  hipError_t e;
   if (fc_tab) e = launch_fc_decim(in, lo, fc_tab, kFcRow, out, nd, frames, 1 << K, st);
   else if (K == 2) e = launch_pc_walk4(in, lo, out, nd, frames, p->pc_tab4.as<PcTab4>(), st);
   else e = launch_pc_walk(in, lo, out, nd, frames, p->pc_tab.as<PcTab>(), st);
   if (e != hipSuccess) return hip_fail(e, fc_tab ? "fc_decim launch" : "pc_walk launch");
   mark(p, st, name);
   const EdgeMaps m = edge_maps(p, K, in.len);
-  // submitted after the walk's launch (before it: the same step time, profiles/r06r)
-  e = launch_pc_edge_v(in, lo, p->edge_v.as<float2>(), frames, m.V, m.J, m.r, p->side_st);
-  if (e != hipSuccess) return hip_fail(e, "pc_edge_v launch");
-  e = side.join();
-  if (e == hipSuccess) e = launch_pc_edge_u(p->edge_v.as<float2>(), out, nd, frames, m.U, m.R, m.r, st);
+  e = launch_pc_edge_batch(in, lo, out, nd, frames, m.U, m.V, m.R, m.J, m.r, st);
   if (e != hipSuccess) return hip_fail(e, "pc_edge launch");
   mark(p, st, "pc_edge");
   return ZFFT_OK;

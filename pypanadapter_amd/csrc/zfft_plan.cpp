@@ -337,10 +337,7 @@ int zfft_plan_create(const zfft_config *cfg, const float *window_or_null, zfft_p
     p->user_window.assign(window_or_null, window_or_null + c.n_fft);
   e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->copy_st, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->side_st, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&p->done_ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&p->fork_ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&p->join_ev, hipEventDisableTiming);
   for (int i = 0; i < 2 && e == hipSuccess; ++i) {
     e = hipEventCreateWithFlags(&p->h2d_ev[i], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p->comp_ev[i], hipEventDisableTiming);
@@ -390,7 +387,7 @@ int zfft_plan_destroy(zfft_plan *p) {
   (void)hipSetDevice(p->cfg.device);
   // every stream idle before anything it may still use goes away
   if (p->has_work) (void)hipEventSynchronize(p->done_ev);
-  for (hipStream_t s : {p->stream, p->side_st, p->copy_st})
+  for (hipStream_t s : {p->stream, p->copy_st})
     if (s) (void)hipStreamSynchronize(s);
   if (p->row_pin) (void)hipHostFree(p->row_pin);
   tap_release(p);  // (its page-locked staging)
@@ -398,10 +395,9 @@ int zfft_plan_destroy(zfft_plan *p) {
   demod_release(p);
   resamp_release(p);
   for (hipEvent_t ev : p->events) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : {p->done_ev, p->fork_ev, p->join_ev, p->h2d_ev[0], p->h2d_ev[1], p->comp_ev[0],
-                        p->comp_ev[1]})
+  for (hipEvent_t ev : {p->done_ev, p->h2d_ev[0], p->h2d_ev[1], p->comp_ev[0], p->comp_ev[1]})
     if (ev) (void)hipEventDestroy(ev);
-  for (hipStream_t s : {p->stream, p->side_st, p->copy_st})
+  for (hipStream_t s : {p->stream, p->copy_st})
     if (s) (void)hipStreamDestroy(s);
   delete p;  // frees the device buffers (DevBuf)
   return ZFFT_OK;

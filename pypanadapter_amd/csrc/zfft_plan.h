@@ -182,10 +182,8 @@ struct zfft_plan {
   hipEvent_t done_ev = nullptr;
   hipStream_t done_st = nullptr;
   bool has_work = false;
-  // the walk's frame-end sums V^T x run on side_st beside it (fork_ev / join_ev), into edge_v
-  hipStream_t side_st = nullptr;
-  hipEvent_t fork_ev = nullptr, join_ev = nullptr;
-  DevBuf edge_v;
+  // (the walk's and FC's frame-end maps follow the decimator on its own stream and keep V^T x in
+  // LDS: no stream, event or buffer of theirs here)
   // FC decimator (paths 6, 7): W_M twiddles (M = 8192 / the head's zoom), then one C row per LO frequency; fc_built holds the
   // f_lo / fs ratios the rows were built for (rebuilt when they change; empty: not built)
   DevBuf fc_tab;
