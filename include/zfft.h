@@ -1028,6 +1028,87 @@ int zfft_resamp_info(const zfft_plan *plan, double *group_delay, double *rate_ra
 /* No plan, no GPU.  Rule 6: L taps_per_phase float64 values. */
 int zfft_resamp_design(int32_t L, int32_t M, int32_t taps_per_phase, double beta, double *h_out);
 
+/* Level bank: look-ahead gain control (AGC), squelch and a level meter on K real float32 lanes on
+ * the device -- the link between the demodulator's audio and the resampler's PCM, whose one
+ * `scale` cannot serve channels 80 dB apart.  Finite memory and feed-forward on an absolute block
+ * grid, not a recursive attack / release filter: every operation is a max, one division, one
+ * subtraction, one fused multiply-add and one product, so the outputs do not depend on how the
+ * stream is cut.  Off by default: a plan that never calls zfft_plan_level allocates and launches
+ * nothing.  The rule (reference and float32 model: tests/level_ref.py):
+ *   0. input: float32 on the device, time-major, as the resampler's rule 0: lane s at step n is
+ *      x[n step_stride + s], s < K, 1 <= K <= 2048, step_stride in floats in [K, 2^31].
+ *      zfft_demod_push_device's output is (K, step_stride) = (streams, streams); a subset of
+ *      neighbouring lanes is read in place by offsetting the pointer and keeping the stride.  An
+ *      optional key d_key of the same shape with its own key_stride is the side chain: the gains
+ *      come from the key, the samples from x (FM audio gated by the same channels' POWER trace from
+ *      a second plan's demodulator).  d_key = NULL: the key is x.
+ *   1. parameters: block length B, a power of two in [8, 1024]; hold H in blocks, in [0, 4096];
+ *      float32 target, gmax, floor, each in [2^-60, 2^60]; float32 squelch, 0 (off) or in
+ *      [2^-60, 2^60].  Anything else is ZFFT_EINVAL.
+ *   2. count: the bank counts steps n = 0, 1, ... from zfft_plan_level, or from
+ *      zfft_level_reset(plan, n0), which restarts the count at n_r = n0 (0 <= n0 <= 2^62) and
+ *      zeroes the carry.  Block b is the steps [b B, (b + 1) B) of that absolute axis.  x and the
+ *      key are 0 before n_r, so every block before the start has peak 0.  The count and the carry
+ *      are the bank's own.
+ *   3. block peak: P[b, s] = max over the block of m(key_s[n]), m(v) = 0 where v is NaN, else
+ *      min(|v|, 2^60).  With this cap and rule 1's ranges no gain is denormal, or zero by underflow.
+ *   4. envelope and block gain: E[b, s] = max(P[b - H .. b, s]);
+ *      G[b, s] = min(gmax, target / max(E, floor)) in float32, the division correctly rounded;
+ *      G = 0 where squelch > 0 and E < squelch.  (A fixed gain c with squelch alone: gmax = c,
+ *      target = 2^60.)
+ *   5. step gain: for n = b B + i, g_lo = min(G[b - 1], G[b]), g_hi = min(G[b], G[b + 1]),
+ *      d = g_hi - g_lo rounded once, g = fma(float32(i) / B, d, g_lo); i / B is exact.  The gain
+ *      ramps down during the block before a louder one (the look-ahead attack), up during the
+ *      first block after the hold ends, and within block b never exceeds G[b] but for rounding.
+ *   6. output: y[n, s] = g x_s[n], one rounded product; time-major, out[j K + s] for emitted step
+ *      j of the push.  A NaN sample is NaN in its own output and nowhere else; an infinity counts
+ *      as 2^60 in the peak and is itself +-inf, or NaN where g = 0.  For finite |x| <= 2^60,
+ *      |y| <= target (1 + 2^-21): with the key x, |x_s[n]| <= P[b] <= E[b], and the exact ramp lies
+ *      between g_lo and g_hi, both at most G[b]; four roundings of at most 2^-24 each stand between
+ *      target / E[b] and y -- the division, d (an error of at most 2^-24 G[b] in g), the fma and the
+ *      product -- and (1 + 2^-24)^4 < 1 + 2^-21.
+ *   7. push: block b can be emitted once block b + 1 is complete.  With
+ *      emitted(N) = max(n_r, B (floor(N / B) - 1)), a push of `steps` at count n0 emits the steps
+ *      [emitted(n0), emitted(n0 + steps)) (zfft_level_steps, for the next push; a pure host
+ *      function).  The latency is between B and 2 B - 1 steps (zfft_level_info), not compensated.
+ *      To end a stream push 2 B zeros.
+ *   8. carry: per lane the bank carries the at most 2 B - 1 unemitted steps of x, the running peak
+ *      of the incomplete block and the peaks of the last H + 2 complete blocks (H + 3 values: what
+ *      the next emitted blocks still need), all on the device.  The outputs are the same
+ *      bit for bit however the stream is cut into pushes, pushes shorter than the carry and pushes
+ *      that emit nothing included, and whichever form of the kernels runs.
+ *   9. meter: zfft_level_meter(plan, env_out, gain_out) is synchronous and returns K floats each:
+ *      E and G of the newest complete block of every lane; before any block is complete E = 0 and
+ *      G is rule 4's for E = 0.  The bank's S-meter, and "which channels are open" (G > 0).
+ * zfft_level_push_device is enqueued on its stream with no sync, ordered after earlier work on
+ * that stream and after the plan's earlier calls on any stream (a push longer than any before
+ * first grows the bank's work arrays, which waits); d_out must hold zfft_level_steps x K floats
+ * and not overlap d_x or d_key.  Every zfft_level_* call on a plan with the bank off returns
+ * ZFFT_EINVAL ("level is off"; zfft_level_shape after reporting zeros).  With zfft_plan_timing on a
+ * push reports its launches as "level_peaks", "level_gains" (where it emits) and "level_apply". */
+/* n_lanes = 0: off, frees everything.  Otherwise n_lanes, block, hold, target, gmax, floor and
+ * squelch as rules 0 and 1, anything else ZFFT_EINVAL.  A call restarts the count at 0. */
+int zfft_plan_level(zfft_plan *plan, int32_t n_lanes, int32_t block, int32_t hold, float target, float gmax, float floor,
+                    float squelch);
+int zfft_level_shape(const zfft_plan *plan, int32_t *n_lanes, int32_t *block, int32_t *hold, float *target, float *gmax,
+                     float *floor, float *squelch);
+/* the steps a push of `steps` (0 .. 2^31 - 1) now would emit; a pure host function of the count */
+int zfft_level_steps(const zfft_plan *plan, int64_t steps, int64_t *outputs);
+/* steps (1 .. 2^31 - 1; 0 is ZFFT_OK and does nothing) of the K lanes on the device, rule 0;
+ * d_key NULL (key_stride ignored) or the key */
+int zfft_level_push_device(zfft_plan *plan, const void *d_x, int64_t steps, int64_t step_stride, const void *d_key,
+                           int64_t key_stride, void *d_out, void *stream);
+/* host input ((steps - 1) step_stride + K float32), key (NULL, or the same shape and stride) and
+ * outputs; outputs_out (or NULL) as zfft_level_steps before the push; synchronous */
+int zfft_level_push(zfft_plan *plan, const void *x, const void *key, int64_t steps, int64_t step_stride, void *out,
+                    int64_t *outputs_out);
+int zfft_level_state(zfft_plan *plan, uint64_t *steps_seen);
+int zfft_level_reset(zfft_plan *plan, int64_t n0);
+/* latency_min = B and latency_max = 2 B - 1 steps; rate_ratio = 1 output per step */
+int zfft_level_info(const zfft_plan *plan, double *latency_min, double *latency_max, double *rate_ratio);
+/* rule 9: K floats each; synchronous */
+int zfft_level_meter(zfft_plan *plan, float *env_out, float *gain_out);
+
 const char *zfft_last_error(void);
 int zfft_device_count(void);
 int zfft_version(void);

@@ -103,6 +103,8 @@ EXPORTS = [
     "zfft_demod_push", "zfft_demod_state", "zfft_demod_reset", "zfft_demod_info", "zfft_demod_design",
     "zfft_plan_resamp", "zfft_resamp_shape", "zfft_resamp_steps", "zfft_resamp_push_device", "zfft_resamp_push",
     "zfft_resamp_state", "zfft_resamp_reset", "zfft_resamp_info", "zfft_resamp_design",
+    "zfft_plan_level", "zfft_level_shape", "zfft_level_steps", "zfft_level_push_device", "zfft_level_push",
+    "zfft_level_state", "zfft_level_reset", "zfft_level_info", "zfft_level_meter",
 ]
 
 _lib = None
@@ -279,6 +281,15 @@ def load(path: str = ""):
         "zfft_resamp_reset": (ctypes.c_int, [P, I64]),
         "zfft_resamp_info": (ctypes.c_int, [P, ctypes.POINTER(D), ctypes.POINTER(D)]),
         "zfft_resamp_design": (ctypes.c_int, [I32, I32, I32, D, P]),
+        "zfft_plan_level": (ctypes.c_int, [P, I32, I32, I32] + [ctypes.c_float] * 4),
+        "zfft_level_shape": (ctypes.c_int, [P] + [ctypes.POINTER(I32)] * 3 + [ctypes.POINTER(ctypes.c_float)] * 4),
+        "zfft_level_steps": (ctypes.c_int, [P, I64, ctypes.POINTER(I64)]),
+        "zfft_level_push_device": (ctypes.c_int, [P, P, I64, I64, P, I64, P, P]),
+        "zfft_level_push": (ctypes.c_int, [P, P, P, I64, I64, P, P]),
+        "zfft_level_state": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_uint64)]),
+        "zfft_level_reset": (ctypes.c_int, [P, I64]),
+        "zfft_level_info": (ctypes.c_int, [P, ctypes.POINTER(D), ctypes.POINTER(D), ctypes.POINTER(D)]),
+        "zfft_level_meter": (ctypes.c_int, [P, P, P]),
         "zfft_colormap_lut": (ctypes.c_int, [ctypes.c_char_p, P]),
         "zfft_waterfall_colormap": (ctypes.c_int, [P, ctypes.c_char_p]),
         "zfft_waterfall_levels": (ctypes.c_int, [P, D, D]),

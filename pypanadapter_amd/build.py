@@ -10,12 +10,12 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libzfft.so")
 SOURCES = ["zfft_kernels.hip", "xa_kernels.hip", "pc_kernels.hip", "fc_kernels.hip", "fc2_kernels.hip",
-           "detect_kernels.hip", "detect_local_kernels.hip", "track_kernels.hip", "view_kernels.hip", "history_kernels.hip", "tap_kernels.hip", "chan_kernels.hip", "demod_kernels.hip", "resamp_kernels.hip", "zfft_plan.cpp",
+           "detect_kernels.hip", "detect_local_kernels.hip", "track_kernels.hip", "view_kernels.hip", "history_kernels.hip", "tap_kernels.hip", "chan_kernels.hip", "demod_kernels.hip", "resamp_kernels.hip", "level_kernels.hip", "zfft_plan.cpp",
            "zfft_schedule.cpp", "zfft_decim.cpp", "zfft_welch_plan.cpp", "zfft_welch.cpp",
            "zfft_waterfall.cpp", "zfft_persist.cpp", "zfft_detect_plan.cpp", "zfft_detect.cpp", "zfft_track_plan.cpp", "zfft_track.cpp", "zfft_view_plan.cpp",
-           "zfft_viewport.cpp", "zfft_history_plan.cpp", "zfft_history.cpp", "zfft_stream.cpp", "zfft_tap_plan.cpp", "zfft_tap.cpp", "zfft_chan_plan.cpp", "zfft_chan.cpp", "zfft_demod_plan.cpp", "zfft_demod.cpp", "zfft_resamp_plan.cpp", "zfft_resamp.cpp", "xa_tables.cpp",
+           "zfft_viewport.cpp", "zfft_history_plan.cpp", "zfft_history.cpp", "zfft_stream.cpp", "zfft_tap_plan.cpp", "zfft_tap.cpp", "zfft_chan_plan.cpp", "zfft_chan.cpp", "zfft_demod_plan.cpp", "zfft_demod.cpp", "zfft_resamp_plan.cpp", "zfft_resamp.cpp", "zfft_level_plan.cpp", "zfft_level.cpp", "xa_tables.cpp",
            "pc_tables.cpp", "zfft_ring.cpp", "windows.cpp"]
-HEADERS = ["zfft_internal.h", "zfft_plan.h", "zfft_schedule.h", "zfft_welch_plan.h", "zfft_dif_addr.h", "zfft_detect_plan.h", "zfft_detect_keys.h", "zfft_track_plan.h", "zfft_view_plan.h", "zfft_history_plan.h", "zfft_stream_plan.h", "zfft_stream.h", "zfft_tap_plan.h", "zfft_chan_plan.h", "zfft_demod_plan.h", "zfft_resamp_plan.h", "zfft_median_bias.h", "zfft_device.h", "zfft_fft.h", "zfft_pairs.h", "fc_prefetch_plan.h", "cheby1_q2.h", "pc_edge_maps.h", os.path.join("..", "..", "include", "zfft.h")]
+HEADERS = ["zfft_internal.h", "zfft_plan.h", "zfft_schedule.h", "zfft_welch_plan.h", "zfft_dif_addr.h", "zfft_detect_plan.h", "zfft_detect_keys.h", "zfft_track_plan.h", "zfft_view_plan.h", "zfft_history_plan.h", "zfft_stream_plan.h", "zfft_stream.h", "zfft_tap_plan.h", "zfft_chan_plan.h", "zfft_demod_plan.h", "zfft_resamp_plan.h", "zfft_level_plan.h", "zfft_median_bias.h", "zfft_device.h", "zfft_fft.h", "zfft_pairs.h", "fc_prefetch_plan.h", "cheby1_q2.h", "pc_edge_maps.h", os.path.join("..", "..", "include", "zfft.h")]
 ARCH = os.environ.get("ZFFT_OFFLOAD_ARCH", "gfx950")
 
 

@@ -1,10 +1,10 @@
 // Internal declarations shared by the host files (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp,
 // zfft_waterfall.cpp, zfft_persist.cpp, zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp,
-// zfft_history.cpp, zfft_stream.cpp, zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp, zfft_resamp.cpp, the table builders
+// zfft_history.cpp, zfft_stream.cpp, zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp, zfft_resamp.cpp, zfft_level.cpp, the table builders
 // xa_tables.cpp and pc_tables.cpp) and the HIP kernels
 // (zfft_kernels.hip, xa_kernels.hip, pc_kernels.hip, fc_kernels.hip, fc2_kernels.hip,
 // detect_kernels.hip, detect_local_kernels.hip, track_kernels.hip, view_kernels.hip,
-// history_kernels.hip, tap_kernels.hip, chan_kernels.hip, demod_kernels.hip, resamp_kernels.hip).  Not part of the C-ABI.
+// history_kernels.hip, tap_kernels.hip, chan_kernels.hip, demod_kernels.hip, resamp_kernels.hip, level_kernels.hip).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "zfft_chan_plan.h"    // the channeliser's forms (ChanForm)
 #include "zfft_demod_plan.h"   // the demodulator bank's forms (DemodForm, DemodCut)
 #include "zfft_resamp_plan.h"  // the resampler bank's forms (ResampForm, ResampCut)
+#include "zfft_level_plan.h"   // the level bank's forms (LevelForm, LevelCut)
 #include "zfft_detect_plan.h"  // the row detector's forms (DetectForm)
 #include "zfft_history_plan.h"  // the row history's quantiser and forms (HistQuant, HistForm)
 #include "zfft_tap_plan.h"     // the channel taps' forms and items (TapForm, TapItems)
@@ -553,6 +554,18 @@ hipError_t launch_demod_mode(uint32_t *par, int s_first, int s_count, uint32_t m
 hipError_t launch_resamp_push(const float *x, int64_t steps, int64_t step_stride, const ResampForm &f, const ResampCut &c,
                               int format, float scale, const float *hp, const float *carry_old, float *carry_new,
                               void *out, hipStream_t st);
+// Level bank (zfft.h's rule of zfft_plan_level; level_kernels.hip): the three launches of one push,
+// as choose_level and level_cut tiled it.  A carry holds (2 B - 1) K unemitted steps, K running
+// peaks and (H + 2) K block peaks; pk the push's c.npk x K peaks, gk its c.nq x K block gains.
+// peaks: the key's blocks into pk and carry_new's running peak.  gains (only where c.outs > 0):
+// pk into gk with par = {target, gmax, floor, squelch}.  apply: out[j * K + lane] and the rest of
+// carry_new.  x, key, out, the carries, pk and gk do not overlap.
+hipError_t launch_level_peaks(const float *key, int64_t key_stride, const LevelForm &f, const LevelCut &c,
+                              const float *carry_old, float *carry_new, float *pk, hipStream_t st);
+hipError_t launch_level_gains(const LevelForm &f, const LevelCut &c, const float par[4], const float *pk, float *gk,
+                              hipStream_t st);
+hipError_t launch_level_apply(const float *x, int64_t x_stride, const LevelForm &f, const LevelCut &c, const float *carry_old,
+                              float *carry_new, const float *pk, const float *gk, float *out, hipStream_t st);
 // out[f][i] = in(f, i) (* lo[i] when lo) as complex64, natural layout, frames x len.
 hipError_t launch_fill_c64(float2 *out, int64_t n, float re, float im, hipStream_t st);
 hipError_t launch_ingest(const InDesc &in, const float2 *lo, float2 *out, int frames,

@@ -394,6 +394,7 @@ int zfft_plan_destroy(zfft_plan *p) {
   chan_release(p);
   demod_release(p);
   resamp_release(p);
+  level_release(p);
   for (hipEvent_t ev : p->events) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : {p->done_ev, p->h2d_ev[0], p->h2d_ev[1], p->comp_ev[0], p->comp_ev[1]})
     if (ev) (void)hipEventDestroy(ev);

@@ -1,7 +1,7 @@
 // zfft_plan.h -- the plan object and the helpers every host file of libzfft.so shares
 // (zfft_plan.cpp, zfft_decim.cpp, zfft_welch.cpp, zfft_waterfall.cpp, zfft_persist.cpp,
 // zfft_detect.cpp, zfft_track.cpp, zfft_viewport.cpp, zfft_history.cpp, zfft_stream.cpp,
-// zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp, zfft_resamp.cpp).  Not part of the C-ABI.
+// zfft_tap.cpp, zfft_chan.cpp, zfft_demod.cpp, zfft_resamp.cpp, zfft_level.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@ struct TapState;   // zfft_tap.cpp
 struct ChanState;  // zfft_chan.cpp
 struct DemodState;  // zfft_demod.cpp
 struct ResampState;  // zfft_resamp.cpp
+struct LevelState;  // zfft_level.cpp
 
 // A grow-only device buffer, freed with its owner.
 struct DevBuf {
@@ -175,6 +176,8 @@ struct zfft_plan {
   zfft::DemodState *demod = nullptr;
   // resampler bank (zfft_plan_resamp; zfft_resamp.cpp): null = off (nothing allocated); the state is that file's
   zfft::ResampState *resamp = nullptr;
+  // level bank (zfft_plan_level; zfft_level.cpp): null = off (nothing allocated); the state is that file's
+  zfft::LevelState *level = nullptr;
   // Ordering across streams: every call that enqueues work first makes its stream wait for
   // the plan's previous work (done_ev, recorded on done_st), then records done_ev after its
   // own; the workspaces, tables and the ring are thus used in call order whatever streams the
@@ -276,6 +279,10 @@ void demod_release(zfft_plan *p);
 // --- zfft_resamp.cpp ---
 // Frees the resampler bank and switches it off (the caller has waited for the plan's work).
 void resamp_release(zfft_plan *p);
+
+// --- zfft_level.cpp ---
+// Frees the level bank and switches it off (the caller has waited for the plan's work).
+void level_release(zfft_plan *p);
 
 // --- zfft_welch.cpp ---
 // The Welch rows (or lines) of `frames` decimated frames of Ld samples at x into d_rows, by the

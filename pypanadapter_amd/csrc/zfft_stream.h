@@ -1,5 +1,5 @@
 // zfft_stream.h -- the host path the producers on a sample stream share (zfft_tap.cpp,
-// zfft_chan.cpp, zfft_demod.cpp, zfft_resamp.cpp): the count and its limits, the two
+// zfft_chan.cpp, zfft_demod.cpp, zfft_resamp.cpp, zfft_level.cpp): the count and its limits, the two
 // alternating carries and the staging of a host push.  The counting rule itself is pure
 // (zfft_stream_plan.h).  Not part of the C-ABI.
 #pragma once

@@ -983,6 +983,95 @@ class ZoomFFT:
         check(self.lib.zfft_resamp_info(self._plan, ctypes.byref(gd), ctypes.byref(rr)), "zfft_resamp_info")
         return {"group_delay": gd.value, "rate_ratio": rr.value}
 
+    # ---------------------------------------------------------------- level bank
+    def set_level(self, lanes: int, block: int = 64, hold: int = 0, target: float = 0.5, gmax: float = 1e4,
+                  floor: float = 1e-6, squelch: float = 0.0) -> None:
+        """Level bank (zfft_plan_level): look-ahead gain control and squelch on `lanes` (at most
+        2048) real float32 lanes on the device -- what `demod_push_device` writes -- between the
+        demodulator and the resampler.  Per block of `block` steps (a power of two, 8 .. 1024) and
+        lane, the gain is min(gmax, target / max(E, floor)), E the key's peak over the block and the
+        `hold` (0 .. 4096) before it, 0 where E < squelch (squelch = 0: no squelch); it ramps over
+        the block before a louder one, so the output stays within target, B to 2 B - 1 steps late.
+        set_level(0) turns it off and frees it.  A call restarts the step count.  The rule is in
+        include/zfft.h, reproducible in numpy (tests/level_ref.py)."""
+        if int(lanes) == 0:
+            check(self.lib.zfft_plan_level(self._plan, 0, 0, 0, 0.0, 0.0, 0.0, 0.0), "zfft_plan_level")
+            return
+        check(self.lib.zfft_plan_level(self._plan, int(lanes), int(block), int(hold), float(target), float(gmax),
+                                       float(floor), float(squelch)), "zfft_plan_level")
+
+    def level_shape(self):
+        """(lanes, block, hold, target, gmax, floor, squelch), the four levels as float32 took them."""
+        v = [ctypes.c_int32() for _ in range(3)] + [ctypes.c_float() for _ in range(4)]
+        check(self.lib.zfft_level_shape(self._plan, *[ctypes.byref(x) for x in v]), "zfft_level_shape")
+        return tuple(x.value for x in v)
+
+    def level_steps(self, steps: int) -> int:
+        """Steps a push of `steps` steps now would emit."""
+        v = ctypes.c_int64()
+        check(self.lib.zfft_level_steps(self._plan, int(steps), ctypes.byref(v)), "zfft_level_steps")
+        return v.value
+
+    def level_push(self, x, key=None) -> np.ndarray:
+        """The next steps of the lanes from the host: (steps, lanes) float32 (1-D for one lane), and
+        optionally a key of the same shape the gains are taken from; returns (emitted, lanes)
+        float32.  Synchronous."""
+        k = self.level_shape()[0]
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        if x.ndim != 2 or x.shape[1] != k:
+            raise ValueError("level_push takes (steps, lanes) float32")
+        kp = None
+        if key is not None:
+            key = np.ascontiguousarray(key, dtype=np.float32)
+            if key.reshape(-1, 1).shape == x.shape:
+                key = key.reshape(-1, 1)
+            if key.shape != x.shape:
+                raise ValueError("level_push: the key has the samples' shape")
+            kp = key.ctypes.data_as(ctypes.c_void_p)
+        out = np.empty((self.level_steps(x.shape[0]), k), dtype=np.float32)
+        check(self.lib.zfft_level_push(self._plan, x.ctypes.data_as(ctypes.c_void_p), kp, x.shape[0], k,
+                                       out.ctypes.data_as(ctypes.c_void_p), None), "zfft_level_push")
+        return out
+
+    def level_push_device(self, d_x_ptr: int, steps: int, step_stride: int, d_out_ptr: int, d_key_ptr: int = 0,
+                          key_stride: int = 0, stream: int = 0) -> None:
+        """`steps` steps on the device, lane s at step n at float32 index n * step_stride + s
+        ((streams, streams) for demod_push_device's output), the key (0: the samples themselves)
+        at n * key_stride + s; level_steps(steps) x lanes float32 into d_out_ptr; enqueued on
+        `stream`, no sync."""
+        check(self.lib.zfft_level_push_device(self._plan, ctypes.c_void_p(d_x_ptr), int(steps), int(step_stride),
+                                              ctypes.c_void_p(d_key_ptr or None), int(key_stride),
+                                              ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream or None)),
+              "zfft_level_push_device")
+
+    def level_state(self) -> int:
+        """The steps counted so far."""
+        v = ctypes.c_uint64()
+        check(self.lib.zfft_level_state(self._plan, ctypes.byref(v)), "zfft_level_state")
+        return v.value
+
+    def level_reset(self, n0: int = 0) -> None:
+        """Restart the step count at n0 with an all-zero past; the shape and the levels stay."""
+        check(self.lib.zfft_level_reset(self._plan, int(n0)), "zfft_level_reset")
+
+    def level_info(self) -> dict:
+        """latency_min and latency_max (block and 2 block - 1 steps: reported, not compensated) and
+        rate_ratio (1)."""
+        a, b, rr = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        check(self.lib.zfft_level_info(self._plan, ctypes.byref(a), ctypes.byref(b), ctypes.byref(rr)), "zfft_level_info")
+        return {"latency_min": a.value, "latency_max": b.value, "rate_ratio": rr.value}
+
+    def level_meter(self):
+        """(envelope, gain): float32 arrays of one value a lane, of the newest complete block.
+        Synchronous."""
+        k = self.level_shape()[0]
+        env, gain = np.empty(k, np.float32), np.empty(k, np.float32)
+        check(self.lib.zfft_level_meter(self._plan, env.ctypes.data_as(ctypes.c_void_p), gain.ctypes.data_as(ctypes.c_void_p)),
+              "zfft_level_meter")
+        return env, gain
+
     # ---------------------------------------------------------------- display viewport
     def set_viewport(self, height: int, width: int, col0: int = 0, col1: int | None = None,
                      detector: str = "max", rows_per_line: int = 1) -> None:

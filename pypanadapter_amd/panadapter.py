@@ -936,6 +936,11 @@ class Resampler:
         return cls(demod._plan, info[0], Fraction(demod.rate_in) / info[2], rate_out, format=format, **kw)
 
     @classmethod
+    def for_level(cls, level: "LevelControl", rate_out: float, format: str = "f32", **kw):
+        """One lane per lane of `level`, at its rate; `push` takes what `level.push` returns."""
+        return cls(level._plan, level.lanes, Fraction(level.rate), rate_out, format=format, **kw)
+
+    @classmethod
     def for_tap(cls, tap: "Tap", rate_out: float, slot: int | None = None, **kw):
         """Complex in, complex out: the open tap in `slot` (default: the only open one) as two
         lanes; `push` takes that slot's array of `tap.push` and returns complex64."""
@@ -974,6 +979,82 @@ class Resampler:
 
     def reset(self, n0: int = 0) -> None:
         self._plan.resamp_reset(n0)
+
+
+class LevelControl:
+    """Look-ahead gain control, squelch and a level meter on what a `Demodulator` pushes, on the
+    device (ZoomFFT.set_level; the rule is in include/zfft.h): per block of `block` steps and lane,
+    the gain that brings the envelope -- the peak over the block and `hold` blocks before it -- to
+    `target`, at most `gmax`, 0 below `squelch`; it ramps over the block before a louder one, so
+    the output stays within target, and comes `block` to 2 block - 1 steps late.
+
+        audio = Demodulator.for_channelizer(bank, "am", audio_decim=4)      # 18.75 kHz
+        agc = LevelControl.for_demodulator(audio, target=0.5, attack_s=3e-3, hold_s=0.25, squelch=1e-4)
+        pcm = Resampler.for_level(agc, 48e3, format="s16")
+        s = pcm.push(agc.push(audio.push(bank.push(chunk))))                 # (outputs, 64) int16
+        open_now = agc.meter()["open"]                                        # which channels carry something
+
+    The bank lives on its source's plan, so a caller who keeps the audio on the device can hand it
+    to `plan.level_push_device` with no copy.  `push(y, key=...)` takes the gains from `key` (the
+    side chain: FM audio gated by a power trace).  The latency is reported, not compensated."""
+
+    MIN_BLOCK, MAX_BLOCK, MAX_HOLD = 8, 1024, 4096
+
+    def __init__(self, plan, lanes: int, rate: float, block: int = 64, hold: int = 0, target: float = 0.5,
+                 gmax: float = 1e4, floor: float = 1e-6, squelch: float | None = None):
+        self._plan, self.lanes, self.rate = plan, int(lanes), float(rate)
+        self.block, self.hold = int(block), int(hold)
+        if self.block < self.MIN_BLOCK or self.block > self.MAX_BLOCK or self.block & (self.block - 1):
+            raise ValueError(f"block = {self.block}: not a power of two in [{self.MIN_BLOCK}, {self.MAX_BLOCK}]")
+        if not 0 <= self.hold <= self.MAX_HOLD:
+            raise ValueError(f"hold = {self.hold} blocks: outside [0, {self.MAX_HOLD}]")
+        plan.set_level(self.lanes, self.block, self.hold, target, gmax, floor, 0.0 if squelch is None else squelch)
+
+    @classmethod
+    def for_demodulator(cls, demod: "Demodulator", target: float = 0.5, attack_s: float = 3e-3, hold_s: float = 0.25,
+                        squelch: float | None = None, **kw):
+        """One lane per stream of `demod`; `push` takes what `demod.push` returns.  The block is
+        the power of two nearest attack_s x the audio rate (in the ratio's sense), clipped to
+        [8, 1024]; the hold ceil(hold_s x rate / block) blocks (a ValueError names it past 4096)."""
+        rate = demod.rate
+        want = max(float(attack_s) * rate, 1.0)
+        block = int(min(max(2 ** int(np.floor(np.log2(want) + 0.5)), cls.MIN_BLOCK), cls.MAX_BLOCK))
+        hold = int(np.ceil(float(hold_s) * rate / block))
+        if hold_s < 0 or hold > cls.MAX_HOLD:
+            raise ValueError(f"hold_s = {hold_s} s is {hold} blocks of {block} steps at {rate} Hz: outside [0, {cls.MAX_HOLD}]")
+        return cls(demod._plan, demod.streams, rate, block, hold, target, squelch=squelch, **kw)
+
+    def close(self):
+        """Turns the bank off on the source's plan, which stays the source's."""
+        if self._plan is not None:
+            if self._plan._plan.value:  # (the source may have closed its plan already)
+                self._plan.set_level(0)
+            self._plan = None
+
+    @property
+    def latency(self):
+        """(least, most) steps an output comes after its input: (block, 2 block - 1)."""
+        info = self._plan.level_info()
+        return info["latency_min"], info["latency_max"]
+
+    def steps(self, n: int) -> int:
+        return self._plan.level_steps(n)
+
+    def push(self, y, key=None) -> np.ndarray:
+        """(emitted, lanes) float32 for the next (steps, lanes) float32 of the source."""
+        return self._plan.level_push(y, key)
+
+    def meter(self) -> dict:
+        """envelope and gain of the newest complete block of every lane, and open = gain > 0."""
+        env, gain = self._plan.level_meter()
+        return {"envelope": env, "gain": gain, "open": gain > 0}
+
+    @property
+    def steps_seen(self) -> int:
+        return self._plan.level_state()
+
+    def reset(self, n0: int = 0) -> None:
+        self._plan.level_reset(n0)
 
 
 class Data:
